@@ -15,10 +15,17 @@ generator, seed-indexed per step; no regeneration, copy or PCIe traffic inside t
   (other N, or --workload tsqr: the weak series, 262144 x 512 per GPU)
              TSQR = local QR + ONE RCCL all-gather of the R factors + redundant stacked QR.
 
-Prints ONE JSON line on rank 0: metric fp64 GFLOP/s (F = 2mn^2 - 2n^3/3 per factorisation, whole job),
-plus `roofline` for the dominant kernel (the trailing-update MFMA GEMM; for TSQR the panel kernels),
-`cpu_baseline` (the REAL reference qr.c, or the oracle port of it, on one host core over a bounded
-sample) and the accuracy figures of the north-star (||A-QR||_F/||A||_F, ||Q^T Q - I||_F).
+Prints ONE JSON line on rank 0: metric fp64 GFLOP/s (F = 2mn^2 - 2n^3/3 per factorisation, whole job)
+and `ms_per_step`.  A plain run does only that: set-up, warm-up, the K timed steps, the line.
+
+  --full              also everything else, after the timed steps: `roofline` for the dominant kernel (the
+                      trailing-update MFMA GEMM; for TSQR the panel kernels; HIP events on a sample of the timed
+                      steps plus one fully profiled step), `cpu_baseline` (the REAL reference qr.c, or the oracle
+                      port of it, on one host core over a bounded sample), the accuracy figures of the north-star
+                      (||A-QR||_F/||A||_F, ||Q^T Q - I||_F), panel route counters, the N = 1 TSQR legs and model,
+                      and for N > 1 the un-pipelined latency split, both exchange schedules and the 1-GPU denominator
+  --dump-outputs DIR  after the timed steps: what the last timed step returned to its caller, as float64 .npy
+                      files (dump_outputs(): R and the factored matrix, fixed seeded samples of both)
 """
 import argparse
 import json
@@ -53,8 +60,13 @@ def parse():
                     help="ill-conditioned input: every 128-column panel gets condition ~COND (columns = the panel's first column + "
                          "uniform noise / COND), so the device-side guard refuses every full-width panel -- prices the refusal "
                          "(VERDICT r5 item 4); 0 = the plain uniform matrix")
-    ap.add_argument("--no-check", action="store_true", help="skip the post-run residual/orthogonality check")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline (roofline, accuracy, CPU "
+                         "baseline, route counters, TSQR legs); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (R and the factored matrix, seeded samples) to DIR/<name>.npy")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the post-run residual/orthogonality check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", default="792x384", help="m x n of the bounded multi-panel CPU-baseline sample")
     ap.add_argument("--watchdog", type=float, default=float(os.environ.get("BENCH_WATCHDOG_S", "30")),
                     help="seconds a bring-up phase (rendezvous, communicator, first collective) may take before the process exits 124")
@@ -90,6 +102,38 @@ class Watchdog:
 
 def flops(m, n):
     return 2.0 * m * n * n - 2.0 * n ** 3 / 3.0
+
+
+DUMP_SAMPLE = 1 << 21        # entries per sampled array: 16 MB of float64 each, 32 MB + 2 n doubles in all
+
+
+def dump_outputs(out_dir, A, R, m, n):
+    """What ts.factor(A) hands its caller: R (n x n, column-major, returned) and A overwritten with the factors (R above the
+    diagonal, the Householder vectors below).  Written as float64 .npy:
+      R_diag, R_last_column   the diagonal and the last column of R (the last column depends on every reflector)
+      R_sample                R[i, j], i <= j, at DUMP_SAMPLE positions drawn from a fixed seed (all of the upper triangle,
+                              column by column, when it is smaller)
+      factors_sample          the factored m x n matrix at DUMP_SAMPLE positions drawn from a fixed seed (all of it when smaller)
+    The positions depend on (m, n) only, so two runs with the same arguments dump the same entries."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    Rf, Af = R.reshape(-1), A.reshape(-1)                   # column-major storage: element (i, j) at j * rows + i
+    rng = np.random.default_rng(20250101)
+    if n * (n + 1) // 2 <= DUMP_SAMPLE:
+        i, j = np.triu_indices(n)
+        r_idx = np.sort(j * n + i)
+    else:
+        a, b = rng.integers(0, n, DUMP_SAMPLE), rng.integers(0, n, DUMP_SAMPLE)
+        r_idx = np.maximum(a, b) * n + np.minimum(a, b)
+    a_idx = np.arange(m * n) if m * n <= DUMP_SAMPLE else rng.integers(0, m * n, DUMP_SAMPLE)
+    take = lambda flat, idx: torch.take(flat, torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(flat.device)).cpu().numpy()
+    d = torch.arange(n, device=R.device, dtype=torch.int64) * (n + 1)
+    out = {"R_diag": torch.take(Rf, d).cpu().numpy(), "R_last_column": R[n - 1].cpu().numpy(),
+           "R_sample": take(Rf, r_idx), "factors_sample": take(Af, a_idx)}
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    return sorted(out)
 
 
 def cpu_baseline(sample):
@@ -241,28 +285,34 @@ def main():
         step(i)
     barrier()
     wd.arm(max(300.0, args.watchdog), "timed region")
-    # HIP events on the plan's own streams, inside the timed region -- around the launches of the DOMINANT kernel only (class 0:
-    # the wide update's gemm_nt; tall-skinny: class 2, the panel): every record is two event packets on a stream (~4 us each),
-    # and with all six classes recorded the 16384^2 step took 128.5 ms instead of 126
+    full = args.full
+    # --full: HIP events on the plan's own streams, inside the timed region -- around the launches of the DOMINANT kernel only
+    # (class 0: the wide update's gemm_nt; tall-skinny: class 2, the panel): every record is two event packets on a stream (~4 us
+    # each), and with all six classes recorded the 16384^2 step took 128.5 ms instead of 126
     dominant_cls = 0 if wl in ("c2", "c3") else 2
-    be.plan.set_profile(2 * (1 << dominant_cls))
+    if full:
+        be.plan.set_profile(2 * (1 << dominant_cls))
     # ... and on a SAMPLE of the timed steps (every `stride`-th, at least 4 of them when K allows): the records still bracket the
     # dominant kernel's launches inside the timed region, on the stream they are launched on
     stride = max(1, K // 4)
     t0 = time.perf_counter()
     for i in range(W, W + K):
-        be.plan.pause_profile((i - W) % stride != 0)
+        if full:
+            be.plan.pause_profile((i - W) % stride != 0)
         step(i)
     barrier()
     dt = time.perf_counter() - t0
-    be.plan.pause_profile(False)
-    prof = be.plan.get_profile()
-    # the other classes (W = (V T)^T A2, panel chain, ...): one more factorisation, fully profiled, OUTSIDE the timed region
-    be.plan.set_profile(True)
-    step(W + K)
-    barrier()
-    prof_full = be.plan.get_profile()
-    be.plan.set_profile(False)
+    if args.dump_outputs and rank == 0:     # the last timed step's R and factors (rank 0's shard), before anything factors again
+        dump_outputs(args.dump_outputs, bufs[(W + K - 1) % nbuf], ts.R, m_local, n)
+    if full:
+        be.plan.pause_profile(False)
+        prof = be.plan.get_profile()
+        # the other classes (W = (V T)^T A2, panel chain, ...): one more factorisation, fully profiled, OUTSIDE the timed region
+        be.plan.set_profile(True)
+        step(W + K)
+        barrier()
+        prof_full = be.plan.get_profile()
+        be.plan.set_profile(False)
     wd.arm(max(300.0, args.watchdog), "post-run checks")
     coll_dev = "cuda" if backend == "nccl" else "cpu"
     if world > 1:
@@ -273,9 +323,9 @@ def main():
     total_flops = K * flops(m_total, n)
     value = total_flops / dt / 1e9
 
-    # ---- accuracy (outside the timed region): last factored matrix, thin Q, on-device norms
+    # ---- accuracy (--full, outside the timed region): last factored matrix, thin Q, on-device norms
     acc = {}
-    if not args.no_check:
+    if full and not args.no_check:
         last = (W + K) % nbuf               # the matrix of the extra (fully profiled) step: the last one factored, ts.R is its R
         A = bufs[last]
         ts.sync()
@@ -309,10 +359,10 @@ def main():
         acc = {"resid": float((sums[0] / sums[1]).sqrt().item()), "orth": float(o ** 0.5)}
         del Q, QR, G
 
-    # ---- N > 1 only, outside the timed region: the UN-pipelined latency of one factorisation (every step drained before the
+    # ---- --full, N > 1 only, outside the timed region: the UN-pipelined latency of one factorisation (every step drained before the
     # next starts, so the exchange and the stacked QR are fully exposed) and where it goes
     tsqr_split = None
-    if world > 1:
+    if full and world > 1:
         reps = max(1, min(K, 3))
         for i in range(reps):
             be.fill(bufs[i % nbuf], m_local, n, rank * m_local, m_total, seeds[i % nbuf])
@@ -359,11 +409,11 @@ def main():
                               "and the stacked (world*n) x n matrix (redundant on every rank, latency-bound) is factored "
                               "left-looking while the local QR continues"}
 
-    # ---- N > 1: BOTH exchange schedules, three drained factorisations each, every rank's own numbers (qr_tsqr_set_schedule is collective:
+    # ---- --full, N > 1: BOTH exchange schedules, three drained factorisations each, every rank's own numbers (qr_tsqr_set_schedule is collective:
     # all ranks switch between the same two calls).  The first real multi-GPU run must explain itself: what an all-gather of n*nb doubles per
     # rank costs beside a chip-filling local update, on THIS node, is not known before it.
     by_schedule = None
-    if world > 1 and os.environ.get("BENCH_SCHEDULE_AB", "1") != "0":
+    if full and world > 1 and os.environ.get("BENCH_SCHEDULE_AB", "1") != "0":
         try:
             by_schedule = {}
             real = be.transport == "rccl"
@@ -410,10 +460,10 @@ def main():
         except Exception as e:
             by_schedule = {"error": repr(e)}
 
-    # ---- N > 1, fixed-size configs (C4 / C5): the SAME matrix on ONE GPU, measured by rank 0 in this run (the other ranks wait at
+    # ---- --full, N > 1, fixed-size configs (C4 / C5): the SAME matrix on ONE GPU, measured by rank 0 in this run (the other ranks wait at
     # the next barrier) -- the strong-scaling denominator next to the N-GPU numbers above
     same_1gpu = None
-    if world > 1 and wl in ("c4", "c5") and rank == 0:
+    if full and world > 1 and wl in ("c4", "c5") and rank == 0:
         try:
             one = T.DeviceTSQR(qr, m_total, n, 1, 0, 128)
             A1 = one.new_matrix(m_total, n)
@@ -436,149 +486,151 @@ def main():
         except Exception as e:
             same_1gpu = {"error": repr(e)}
 
-    # ---- roofline of the dominant kernel
-    # dominant kernel: from the timed region; the rest: from the extra profiled step (per-step figures, K_full = 1)
-    if wl in ("c2", "c3"):
-        upd, tn, pan, K_pan = prof["update_nn"], prof_full["vta_tn"], prof_full["panel"], 1
-    else:
-        upd, tn, pan, K_pan = prof_full["update_nn"], prof_full["vta_tn"], prof["panel"], len(range(0, K, stride))
-    measured = None
-    if rank == 0:
+    # ---- --full: roofline of the dominant kernel, and which panel routes the timed plan took
+    roof, panel_routes = None, None
+    if full:
+        # dominant kernel: from the timed region; the rest: from the extra profiled step (per-step figures, K_full = 1)
+        if wl in ("c2", "c3"):
+            upd, tn, pan, K_pan = prof["update_nn"], prof_full["vta_tn"], prof_full["panel"], 1
+        else:
+            upd, tn, pan, K_pan = prof_full["update_nn"], prof_full["vta_tn"], prof["panel"], len(range(0, K, stride))
+        measured = None
+        if rank == 0:
+            try:
+                measured = qr.probe_mfma_f64_tflops()       # sustained v_mfma_f64_16x16x4_f64 rate of THIS device
+            except Exception:
+                measured = None
+        # HBM traffic of the dominant kernel: NOT measured in this run (rocprofv3 counter passes cannot share a process with the
+        # timed region, and crash on CU-masked streams with the ROCm release measured).  The committed round-6 PMC pass (profiles/r06_pmc_traffic.json,
+        # devtools/rounds/r5/scripts_r5_pmc.sh: the same kernel, shapes of every 8th C3 step, no CU masks) is quoted under its own key with
+        # ITS algorithmic bytes, and `traffic` itself only when that file was made for this block size; otherwise null.
+        traffic, traffic_src = None, None
         try:
-            measured = qr.probe_mfma_f64_tflops()       # sustained v_mfma_f64_16x16x4_f64 rate of THIS device
+            tj = json.load(open(os.path.join(ROOT, "profiles", "r06_pmc_traffic.json")))
         except Exception:
-            measured = None
-    # HBM traffic of the dominant kernel: NOT measured in this run (rocprofv3 counter passes cannot share a process with the
-    # timed region, and crash on CU-masked streams on this pool).  The committed round-6 PMC pass (profiles/r06_pmc_traffic.json,
-    # devtools/rounds/r5/scripts_r5_pmc.sh: the same kernel, shapes of every 8th C3 step, no CU masks) is quoted under its own key with
-    # ITS algorithmic bytes, and `traffic` itself only when that file was made for this block size; otherwise null.
-    traffic, traffic_src = None, None
-    try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", "r06_pmc_traffic.json")))
-    except Exception:
-        tj = None
-    gen = 2
-    kname = ("gemm_nt4_kernel<true, 0, 8, 3> (trailing update A2 -= V*Wt^T, W kept transposed; four 4-wave workgroups per CU on 128 x 64 tiles, "
-             "direct-to-LDS k-tiles of 8 in three stages, v_mfma_f64_16x16x4_f64; MI355XQR_NT4=0: the 8-wave gemm_nt_kernel<true, 0, 1>)")
-    if wl in ("c2", "c3") and upd["launches"]:
-        ach = upd["flops"] / (upd["ms"] * 1e-3) / 1e12
-        if tj and wl == "c3" and nb == tj.get("nb") and gen == 2 and "gemm_nt_kernel" in tj:
-            e = tj["gemm_nt_kernel"]                    # (key kept from round 3: the entry is the update kernel of the pass, now gemm_nt4_kernel)
-            traffic = e["hbm_bytes_per_launch"]
-            traffic_src = {"file": "profiles/r06_pmc_traffic.json", "git_head_of_pass": tj.get("git_head"),
-                           "launch_mix": tj.get("config"),
-                           "algorithmic_bytes_per_launch_same_mix": e["algorithmic_bytes_per_launch"],
-                           "ratio_traffic_to_algorithmic": e["ratio"],
-                           "method": "2*FETCH_SIZE + WRITE_SIZE per dispatch (gfx950 correction, MI355X_MICROARCH.md HBM section), "
-                                     "separate rocprofv3 --pmc passes; replayed from the committed file, not measured in this run",
-                           "note": "x1.55: the write-allocated C tiles push the operand tiles of the 128 x 64 tiling (3.75 MB per XCD at a time) out of the 4 MB L2 "
-                                   "and they are fetched again -- from the 256 MB Infinity Cache, which FETCH_SIZE (L2 misses) cannot tell from HBM; with "
-                                   "non-temporal C accesses the refetches go away (-40 %) and nothing gets faster (profiles/r05_nt_ceiling.txt)"}
-        # the committed rocprofv3 --kernel-trace --stats summary of this bench command: the kernel's average duration there, next to the
-        # HIP-event figure of this run (an event bracket also holds two barrier packets and the dispatch latency: ~15 us per launch)
-        rocprof_ref = None
-        try:
-            import csv
-            for row in csv.DictReader(open(os.path.join(ROOT, "profiles", "r06_bench_c3_kernel_stats.csv"))):
-                if wl == "c3" and row["Name"].startswith("void gemm_nt4_kernel<true, 0, 8, 3"):      # (<.., RAG = false>: the aligned instantiation, the only one C3 launches)
-                    ns = float(row["AverageNs"])
-                    rocprof_ref = {"file": "profiles/r06_bench_c3_kernel_stats.csv", "calls": int(row["Calls"]), "avg_launch_ms": ns * 1e-6,
-                                   "achieved_at_that_duration": (upd["flops"] / upd["launches"]) / (ns * 1e-9) / 1e12,
-                                   "note": "same command under rocprofv3 (committed); the launch mix per step is the one timed here"}
-        except Exception:
+            tj = None
+        gen = 2
+        kname = ("gemm_nt4_kernel<true, 0, 8, 3> (trailing update A2 -= V*Wt^T, W kept transposed; four 4-wave workgroups per CU on 128 x 64 tiles, "
+                 "direct-to-LDS k-tiles of 8 in three stages, v_mfma_f64_16x16x4_f64; MI355XQR_NT4=0: the 8-wave gemm_nt_kernel<true, 0, 1>)")
+        if wl in ("c2", "c3") and upd["launches"]:
+            ach = upd["flops"] / (upd["ms"] * 1e-3) / 1e12
+            if tj and wl == "c3" and nb == tj.get("nb") and gen == 2 and "gemm_nt_kernel" in tj:
+                e = tj["gemm_nt_kernel"]                    # (key kept from round 3: the entry is the update kernel of the pass, now gemm_nt4_kernel)
+                traffic = e["hbm_bytes_per_launch"]
+                traffic_src = {"file": "profiles/r06_pmc_traffic.json", "git_head_of_pass": tj.get("git_head"),
+                               "launch_mix": tj.get("config"),
+                               "algorithmic_bytes_per_launch_same_mix": e["algorithmic_bytes_per_launch"],
+                               "ratio_traffic_to_algorithmic": e["ratio"],
+                               "method": "2*FETCH_SIZE + WRITE_SIZE per dispatch (the gfx950 correction of FETCH_SIZE), "
+                                         "separate rocprofv3 --pmc passes; replayed from the committed file, not measured in this run",
+                               "note": "x1.55: the write-allocated C tiles push the operand tiles of the 128 x 64 tiling (3.75 MB per XCD at a time) out of the 4 MB L2 "
+                                       "and they are fetched again -- from the 256 MB Infinity Cache, which FETCH_SIZE (L2 misses) cannot tell from HBM; with "
+                                       "non-temporal C accesses the refetches go away (-40 %) and nothing gets faster (profiles/r05_nt_ceiling.txt)"}
+            # the committed rocprofv3 --kernel-trace --stats summary of this bench command: the kernel's average duration there, next to the
+            # HIP-event figure of this run (an event bracket also holds two barrier packets and the dispatch latency: ~15 us per launch)
             rocprof_ref = None
-        cus_u = None
-        try:
-            cus_u = int(be.plan.update_cus())
-        except Exception:
-            pass
-        roof = {"bound": "mfma",
-                "kernel": kname,
-                "achieved": ach, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": ach / FP64_MATRIX_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                "peak_source": "AMD MI355X datasheet fp64 matrix 78.6 TFLOP/s (MI355X_MICROARCH.md has no fp64 MFMA row)",
-                # back-to-back independent v_mfma_f64_16x16x4_f64 (16 accumulators per wave, inline asm) on all CUs
-                "measured_mfma_f64_sustained_tflops": measured["mfma_f64_tflops"] if measured else None,
-                "frac_of_measured_sustained": ach / measured["mfma_f64_tflops"] if measured else None,
-                "cu_partition_note": ("with look-ahead the wide update runs on the update stream's compute units "
-                                      "(16384^2: 224 of 256, the panel chain owns 32 = 4 compute units of every XCD; smaller problems 192 / 64)"),
-                "update_stream_cus": cus_u,
-                # the same rate against the peak of the compute units the kernel actually runs on (`frac` above stays against the whole
-                # chip, as the contract asks): what the kernel itself leaves on the table, apart from the schedule's CU partition
-                "cus": cus_u,
-                "frac_of_cus_used": (ach / (FP64_MATRIX_PEAK_TFLOPS * cus_u / float(qr.device_info()["compute_units"] or 256))) if cus_u else None,
-                "rocprof_pmc": "profiles/r06_pmc_mfma_lds_util.txt (MfmaUtil, LdsUtil, LdsBankConflict of the same kernel, whole chip: rocprofv3 --pmc crashes on CU-masked streams on this pool)",
-                "ceiling": "profiles/r05_nt_ceiling.txt (same launch mix with the C traffic / the operand loads compiled out: 58.9 / 61.4 TFLOP/s in situ bound any K = 256 kernel on 224 CUs)",
-                "measured_probe": measured,
-                "rocprofv3_same_kernel": rocprof_ref,
-                "launches": upd["launches"], "avg_launch_ms": upd["ms"] / upd["launches"],
-                "profiled_steps_in_timed_region": len(range(0, K, stride)),
-                "algorithmic_flops_per_launch": upd["flops"] / upd["launches"],
-                "algorithmic_bytes_per_launch": upd["bytes"] / upd["launches"],
-                # the OTHER kernel of the update pair in the same shape: Wt = A2^T (V T), from the extra profiled step
-                "companion_tn": (lambda a: {"kernel": "gemm_tn_kernel<4, 4, true, 1> + slab_reduce_kernel (Wt = A2^T (V T); split-K slabs summed in a fixed order)",
-                                            "bound": "mfma", "achieved": a, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                            "frac": (a / FP64_MATRIX_PEAK_TFLOPS) if a else None,
-                                            "traffic": (tj or {}).get("gemm_tn_kernel<4,4,true,1>", {}).get("hbm_bytes_per_launch") if (tj and wl == "c3" and nb == tj.get("nb")) else None,
-                                            "traffic_ratio_to_algorithmic": (tj or {}).get("gemm_tn_kernel<4,4,true,1>", {}).get("ratio") if (tj and wl == "c3" and nb == tj.get("nb")) else None,
-                                            "traffic_note": "x2.28 of algorithmic: A2 is read once per 128-column tile of V T (N / 128 = 2 times at nb 256); the 128 x 256-tile form "
-                                                            "(x1.25, lab knob MI355XQR_TN_WIDE) was re-measured this round at the final code and LOSES 3 ms at C3 "
-                                                            "(profiles/r06_tn_wide_ab.txt): the product is matrix-core bound, the refetches come from the Infinity Cache",
-                                            "launches": tn["launches"], "avg_launch_ms": tn["ms"] / tn["launches"] if tn["launches"] else None})(
-                                     tn["flops"] / (tn["ms"] * 1e-3) / 1e12 if tn["ms"] else None),
-                "panel_ms_per_step": pan["ms"] / K_pan,
-                "other_classes_note": "wide_product_tn and panel_ms_per_step come from one extra, fully profiled factorisation after "
-                                      "the timed region; inside it only the dominant kernel's launches carry HIP events"}
-    else:
-        # tall-skinny: the panel (TSQR leaf kernels + in-panel updates) is the dominant cost; its compulsory HBM
-        # traffic is 16 * mk * w bytes per panel (read + write once)
-        ach = pan["bytes"] / (pan["ms"] * 1e-3) / 1e9 if pan["ms"] else 0.0
-        # measured HBM bytes of the leaf's three streaming kernels (PMC pass of the leaf entry point on a 262144 x 32 leaf,
-        # profiles/r03_pmc_panel_hbm.json), replayed -- not measured in this run; a "launch" here is one outer panel = nb/32 leaves
-        # plus their in-panel updates, whose bytes are not in the counter file
-        ptraffic, psrc = None, None
-        try:
-            # round 4: a 262144-row, 128-column panel takes the full-width route (qr_panel_cqr.hip): PMC passes over one such panel
-            pj = json.load(open(os.path.join(ROOT, "profiles", "r06_pmc_panel_hbm.json")))
-            if m_local == pj["mk"] and nb == pj["w"]:
-                ptraffic = pj["hbm_bytes_per_panel"]
-                psrc = {"file": "profiles/r06_pmc_panel_hbm.json", "covers": pj["covers"], "method": pj["method"] + "; replayed from the committed file"}
-        except Exception:
-            pass
-        # whole-factorisation HBM bytes of this shape (every dispatch: leaf kernels, in-panel products and updates, outer updates),
-        # PMC passes of devtools/rounds/r4/scripts_r4_pmc.sh -- replayed, not measured in this run
-        whole = None
-        try:
-            wj = json.load(open(os.path.join(ROOT, "profiles", "r06_pmc_tsqr_total_traffic.json")))
-            if m_local == wj["m"] and n == wj["n"]:
-                whole = {"file": "profiles/r06_pmc_tsqr_total_traffic.json", "hbm_bytes_per_factorisation": wj["hbm_bytes_per_factorisation"],
-                         "algorithmic_bytes_16mn": wj["algorithmic_bytes_16mn"], "ratio": wj["ratio"],
-                         "achieved_GBps_whole_step": wj["hbm_bytes_per_factorisation"] / (dt / K) / 1e9}
-        except Exception:
-            pass
-        roof = None if not pan["launches"] else {"bound": "hbm", "kernel": "panel factorisation: 128-column panels of > 8192 rows at full width (qr_panel_cqr.hip: cqr_gram / cqr_chol / cqr_stream<Q,G2> / cqr_lu / cqr_vpass kernels; round 4: from 196608 rows), up to 8192 rows in one launch (panel_fused_kernel), others by the leaf chain",
-                "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBPS,
-                "traffic": ptraffic, "traffic_source": psrc, "traffic_whole_factorisation": whole,
-                "launches": pan["launches"], "avg_launch_ms": pan["ms"] / max(pan["launches"], 1),
-                "profiled_steps_in_timed_region": len(range(0, K, stride)),
-                "algorithmic_bytes_per_launch": pan["bytes"] / max(pan["launches"], 1),
-                "note": "algorithmic bytes = 16*mk*nb per outer panel (read + write once); a full-width panel moves 2.6x that in three passes "
-                        "(G1; Q + G2; V -- to one destination when the panel is parked; 3.15x with two, the stand-alone panel of the PMC file) -- its passes cost memory time plus "
-                        "matrix-core time, and two one-workgroup factor kernels (0.12 ms in round 5, 0.27 in round 4) sit between them "
-                        "(DESIGN.md section 3)",
-                "update_nn_tflops": upd["flops"] / (upd["ms"] * 1e-3) / 1e12 if upd["ms"] else None,
-                "measured_probe": measured}
+            try:
+                import csv
+                for row in csv.DictReader(open(os.path.join(ROOT, "profiles", "r06_bench_c3_kernel_stats.csv"))):
+                    if wl == "c3" and row["Name"].startswith("void gemm_nt4_kernel<true, 0, 8, 3"):      # (<.., RAG = false>: the aligned instantiation, the only one C3 launches)
+                        ns = float(row["AverageNs"])
+                        rocprof_ref = {"file": "profiles/r06_bench_c3_kernel_stats.csv", "calls": int(row["Calls"]), "avg_launch_ms": ns * 1e-6,
+                                       "achieved_at_that_duration": (upd["flops"] / upd["launches"]) / (ns * 1e-9) / 1e12,
+                                       "note": "same command under rocprofv3 (committed); the launch mix per step is the one timed here"}
+            except Exception:
+                rocprof_ref = None
+            cus_u = None
+            try:
+                cus_u = int(be.plan.update_cus())
+            except Exception:
+                pass
+            roof = {"bound": "mfma",
+                    "kernel": kname,
+                    "achieved": ach, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": ach / FP64_MATRIX_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                    "peak_source": "AMD MI355X datasheet fp64 matrix 78.6 TFLOP/s",
+                    # back-to-back independent v_mfma_f64_16x16x4_f64 (16 accumulators per wave, inline asm) on all CUs
+                    "measured_mfma_f64_sustained_tflops": measured["mfma_f64_tflops"] if measured else None,
+                    "frac_of_measured_sustained": ach / measured["mfma_f64_tflops"] if measured else None,
+                    "cu_partition_note": ("with look-ahead the wide update runs on the update stream's compute units "
+                                          "(16384^2: 224 of 256, the panel chain owns 32 = 4 compute units of every XCD; smaller problems 192 / 64)"),
+                    "update_stream_cus": cus_u,
+                    # the same rate against the peak of the compute units the kernel actually runs on (`frac` above stays against the whole
+                    # chip, as the contract asks): what the kernel itself leaves on the table, apart from the schedule's CU partition
+                    "cus": cus_u,
+                    "frac_of_cus_used": (ach / (FP64_MATRIX_PEAK_TFLOPS * cus_u / float(qr.device_info()["compute_units"] or 256))) if cus_u else None,
+                    "rocprof_pmc": "profiles/r06_pmc_mfma_lds_util.txt (MfmaUtil, LdsUtil, LdsBankConflict of the same kernel, whole chip: rocprofv3 --pmc crashes on CU-masked streams)",
+                    "ceiling": "profiles/r05_nt_ceiling.txt (same launch mix with the C traffic / the operand loads compiled out: 58.9 / 61.4 TFLOP/s in situ bound any K = 256 kernel on 224 CUs)",
+                    "measured_probe": measured,
+                    "rocprofv3_same_kernel": rocprof_ref,
+                    "launches": upd["launches"], "avg_launch_ms": upd["ms"] / upd["launches"],
+                    "profiled_steps_in_timed_region": len(range(0, K, stride)),
+                    "algorithmic_flops_per_launch": upd["flops"] / upd["launches"],
+                    "algorithmic_bytes_per_launch": upd["bytes"] / upd["launches"],
+                    # the OTHER kernel of the update pair in the same shape: Wt = A2^T (V T), from the extra profiled step
+                    "companion_tn": (lambda a: {"kernel": "gemm_tn_kernel<4, 4, true, 1> + slab_reduce_kernel (Wt = A2^T (V T); split-K slabs summed in a fixed order)",
+                                                "bound": "mfma", "achieved": a, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                                "frac": (a / FP64_MATRIX_PEAK_TFLOPS) if a else None,
+                                                "traffic": (tj or {}).get("gemm_tn_kernel<4,4,true,1>", {}).get("hbm_bytes_per_launch") if (tj and wl == "c3" and nb == tj.get("nb")) else None,
+                                                "traffic_ratio_to_algorithmic": (tj or {}).get("gemm_tn_kernel<4,4,true,1>", {}).get("ratio") if (tj and wl == "c3" and nb == tj.get("nb")) else None,
+                                                "traffic_note": "x2.28 of algorithmic: A2 is read once per 128-column tile of V T (N / 128 = 2 times at nb 256); the 128 x 256-tile form "
+                                                                "(x1.25, lab knob MI355XQR_TN_WIDE) was re-measured this round at the final code and LOSES 3 ms at C3 "
+                                                                "(profiles/r06_tn_wide_ab.txt): the product is matrix-core bound, the refetches come from the Infinity Cache",
+                                                "launches": tn["launches"], "avg_launch_ms": tn["ms"] / tn["launches"] if tn["launches"] else None})(
+                                         tn["flops"] / (tn["ms"] * 1e-3) / 1e12 if tn["ms"] else None),
+                    "panel_ms_per_step": pan["ms"] / K_pan,
+                    "other_classes_note": "wide_product_tn and panel_ms_per_step come from one extra, fully profiled factorisation after "
+                                          "the timed region; inside it only the dominant kernel's launches carry HIP events"}
+        else:
+            # tall-skinny: the panel (TSQR leaf kernels + in-panel updates) is the dominant cost; its compulsory HBM
+            # traffic is 16 * mk * w bytes per panel (read + write once)
+            ach = pan["bytes"] / (pan["ms"] * 1e-3) / 1e9 if pan["ms"] else 0.0
+            # measured HBM bytes of the leaf's three streaming kernels (PMC pass of the leaf entry point on a 262144 x 32 leaf,
+            # profiles/r03_pmc_panel_hbm.json), replayed -- not measured in this run; a "launch" here is one outer panel = nb/32 leaves
+            # plus their in-panel updates, whose bytes are not in the counter file
+            ptraffic, psrc = None, None
+            try:
+                # round 4: a 262144-row, 128-column panel takes the full-width route (qr_panel_cqr.hip): PMC passes over one such panel
+                pj = json.load(open(os.path.join(ROOT, "profiles", "r06_pmc_panel_hbm.json")))
+                if m_local == pj["mk"] and nb == pj["w"]:
+                    ptraffic = pj["hbm_bytes_per_panel"]
+                    psrc = {"file": "profiles/r06_pmc_panel_hbm.json", "covers": pj["covers"], "method": pj["method"] + "; replayed from the committed file"}
+            except Exception:
+                pass
+            # whole-factorisation HBM bytes of this shape (every dispatch: leaf kernels, in-panel products and updates, outer updates),
+            # PMC passes of devtools/rounds/r4/scripts_r4_pmc.sh -- replayed, not measured in this run
+            whole = None
+            try:
+                wj = json.load(open(os.path.join(ROOT, "profiles", "r06_pmc_tsqr_total_traffic.json")))
+                if m_local == wj["m"] and n == wj["n"]:
+                    whole = {"file": "profiles/r06_pmc_tsqr_total_traffic.json", "hbm_bytes_per_factorisation": wj["hbm_bytes_per_factorisation"],
+                             "algorithmic_bytes_16mn": wj["algorithmic_bytes_16mn"], "ratio": wj["ratio"],
+                             "achieved_GBps_whole_step": wj["hbm_bytes_per_factorisation"] / (dt / K) / 1e9}
+            except Exception:
+                pass
+            roof = None if not pan["launches"] else {"bound": "hbm", "kernel": "panel factorisation: 128-column panels of > 8192 rows at full width (qr_panel_cqr.hip: cqr_gram / cqr_chol / cqr_stream<Q,G2> / cqr_lu / cqr_vpass kernels; round 4: from 196608 rows), up to 8192 rows in one launch (panel_fused_kernel), others by the leaf chain",
+                    "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBPS,
+                    "traffic": ptraffic, "traffic_source": psrc, "traffic_whole_factorisation": whole,
+                    "launches": pan["launches"], "avg_launch_ms": pan["ms"] / max(pan["launches"], 1),
+                    "profiled_steps_in_timed_region": len(range(0, K, stride)),
+                    "algorithmic_bytes_per_launch": pan["bytes"] / max(pan["launches"], 1),
+                    "note": "algorithmic bytes = 16*mk*nb per outer panel (read + write once); a full-width panel moves 2.6x that in three passes "
+                            "(G1; Q + G2; V -- to one destination when the panel is parked; 3.15x with two, the stand-alone panel of the PMC file) -- its passes cost memory time plus "
+                            "matrix-core time, and two one-workgroup factor kernels (0.12 ms in round 5, 0.27 in round 4) sit between them "
+                            "(DESIGN.md section 3)",
+                    "update_nn_tflops": upd["flops"] / (upd["ms"] * 1e-3) / 1e12 if upd["ms"] else None,
+                    "measured_probe": measured}
 
-    # which panel routes the timed plan took, and whether a device-side guard fired (include/mi355x_qr.h: qr_plan_route_stats)
-    try:
-        panel_routes = be.plan.route_stats()
-    except Exception:
-        panel_routes = None
+        # which panel routes the timed plan took, and whether a device-side guard fired (include/mi355x_qr.h: qr_plan_route_stats)
+        try:
+            panel_routes = be.plan.route_stats()
+        except Exception:
+            panel_routes = None
 
-    # ---- N = 1 only: the one-GPU leg of the multi-GPU (TSQR, weak scaling) series, so that the N > 1 lines of this
+    # ---- --full, N = 1 only: the one-GPU leg of the multi-GPU (TSQR, weak scaling) series, so that the N > 1 lines of this
     # bench (262144 x 512 per GPU) have their own denominator next to the C3 headline
     weak_base, tsqr_model = None, None
-    if world == 1 and wl == "c3":
+    if full and world == 1 and wl == "c3":
         bufs.clear()
         be.close()
         be = T.DeviceTSQR(qr, 262144, 512, 1, 0, 128)
@@ -646,7 +698,7 @@ def main():
     line = None
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_sample)
         info = qr.device_info()
         line = {
@@ -654,6 +706,7 @@ def main():
             "value": value, "unit": "GFLOP/s", "n_gpus": world, "steps": K, "warmup": W,
             "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": scaling,
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "full": full,           # False: roofline, accuracy, cpu_baseline and the TSQR fields below are not measured (null / {})
             "config": {"workload": desc, "m": m_total, "n": n, "m_per_gpu": m_local, "nb": nb,
                        "ib": args.ib or qr.get_block_size()[1],
                        "flops_per_step": flops(m_total, n), "input_buffers": nbuf,

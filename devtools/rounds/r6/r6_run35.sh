@@ -15,6 +15,6 @@ S="4096x4096x64 2048x2048x64 1024x1024x64 2560x2560x64 3584x3584x64 8192x8192x64
   echo "== half tiles from 8 M elements"; CHECK=1 python3 devtools/tools_perf.py $S 2>&1 | fmt
   done ) > $O/half_tiles_gated.txt 2>&1
 cat $O/half_tiles_gated.txt
-python3 bench.py --workload c2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err; python3 -c "
+python3 bench.py --full --workload c2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err; python3 -c "
 import json; d=json.loads(open('$O/bench_c2.json').read().strip().splitlines()[-1]); print('C2 bench line', d['ms_per_step'], d['value'], d['accuracy'])"
 timeout -k 10 900 python -m pytest tests/test_gpu_multipanel_golden.py tests/test_gpu_qr.py tests/test_gpu_kernels.py -m gpu -x -q > $O/tests.log 2>&1; rc=$?; echo "tests rc=$rc"; tail -3 $O/tests.log

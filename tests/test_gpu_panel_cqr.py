@@ -170,7 +170,7 @@ def test_geqrf_takes_the_full_width_route_on_tall_shapes(qr, m, n, nb):
     assert np.linalg.norm(Q.T @ Q - np.eye(n)) < 1e-12
 
 
-def test_parked_panels_give_the_same_bits_as_v_written_twice(qr):
+def test_parked_panels_give_the_same_bits_as_v_written_twice(qr, tmp_path):
     """Parked full-width panels (tall single-stream plans: V written once, into the caller's array, R of the top block restored from
     the panel workspace behind the update) against MI355XQR_CQR_PARK=0 (child process on the lab library: a measurement knob, read once): the factored array, tau
     and the thin Q must be IDENTICAL -- the update reads the same V values from another place, nothing else changes."""
@@ -197,9 +197,10 @@ def test_parked_panels_give_the_same_bits_as_v_written_twice(qr):
             "A = torch.zeros((n, m), dtype=torch.float64, device='cuda'); tau = torch.zeros((1, n), dtype=torch.float64, device='cuda'); torch.cuda.synchronize()\n"
             "p.fill_uniform(A, m, m, n, seed=31); p.sync(); p.geqrf(A, m, n, m, tau); p.sync()\n"
             "np.save(sys.argv[1], A.cpu().numpy().T); np.save(sys.argv[2], tau.cpu().numpy().ravel())\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.run([sys.executable, "-c", code, "/tmp/park_off_F.npy", "/tmp/park_off_tau.npy"], check=True,
+    fF, ftau = str(tmp_path / "park_off_F.npy"), str(tmp_path / "park_off_tau.npy")
+    subprocess.run([sys.executable, "-c", code, fF, ftau], check=True,
                    env=dict(os.environ, CUDA_QR_AMD_LIB="lab", MI355XQR_CQR_PARK="0"), timeout=300)      # a measurement knob: lab library
-    assert np.array_equal(np.load("/tmp/park_off_F.npy"), F) and np.array_equal(np.load("/tmp/park_off_tau.npy"), tau)
+    assert np.array_equal(np.load(fF), F) and np.array_equal(np.load(ftau), tau)
 
 
 def _ill_conditioned(kind, m, n, seed):

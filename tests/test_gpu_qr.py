@@ -320,7 +320,7 @@ def test_c3_16384_square_properties(qr, nb):
     p.close()
 
 
-def test_lookahead_matches_sequential_schedule(qr, oracle):
+def test_lookahead_matches_sequential_schedule(qr, oracle, tmp_path):
     """Same matrix through the two-stream look-ahead schedule and the single-stream schedule."""
     import subprocess, sys, os, json
     code = ("import sys, json, numpy as np, torch; sys.path.insert(0, %r); import cuda_qr_amd as q;"
@@ -329,7 +329,7 @@ def test_lookahead_matches_sequential_schedule(qr, oracle):
             "R=np.triu(A.cpu().numpy().T[:n]); np.save(sys.argv[1], R)") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for la in ("1", "0"):
-        path = f"/tmp/la_{la}.npy"
+        path = str(tmp_path / f"la_{la}.npy")
         env = dict(os.environ, MI355XQR_LOOKAHEAD=la)
         subprocess.run([sys.executable, "-c", code, path], check=True, env=env)
         outs.append(np.load(path))
@@ -380,7 +380,7 @@ def test_geqrf_dev_on_odd_leading_dimensions_and_misaligned_arrays(qr, oracle, m
     assert np.all(np.isfinite(F[:, :m]))
 
 
-def test_cu_split_that_is_not_a_multiple_of_32(qr, oracle):
+def test_cu_split_that_is_not_a_multiple_of_32(qr, oracle, tmp_path):
     """MI355XQR_SPLIT=48: the dispatcher deals workgroups evenly over the shader engines whatever the mask says, so the one-launch panel
     (workgroups waiting for each other) may only count on whole multiples of 32 of a mask (qrd_stream_cus_coresident); before, its hand-off
     timed out on a 6144-row panel (status -105).  Same R as the single-stream schedule."""
@@ -391,7 +391,7 @@ def test_cu_split_that_is_not_a_multiple_of_32(qr, oracle):
             "R=np.triu(A.cpu().numpy().T[:n]); np.save(sys.argv[1], R)") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for env_add in ({"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "48"}, {"MI355XQR_LOOKAHEAD": "0"}):
-        path = "/tmp/split48_%d.npy" % len(outs)
+        path = str(tmp_path / ("split48_%d.npy" % len(outs)))
         subprocess.run([sys.executable, "-c", code, path], check=True, env=dict(os.environ, **env_add), timeout=300)
         outs.append(np.load(path))
     assert rel(oracle.sign_normalise(outs[0]), oracle.sign_normalise(outs[1])) < 1e-13
@@ -522,7 +522,7 @@ def test_profile_hooks(qr):
     assert 1 <= prof["update_nn"]["launches"] <= n // nb - 1 and prof["panel"]["launches"] == n // nb
     assert prof["update_nn"]["ms"] > 0 and prof["update_nn"]["flops"] > 0
     assert prof["update_nn"]["flops"] == prof["vta_tn"]["flops"]
-    # class mask (what bench.py uses inside its timed region): only the wide update's class 0 carries events
+    # class mask (what bench.py --full uses inside its timed region): only the wide update's class 0 carries events
     full_nn = prof["update_nn"]["launches"]
     p.fill_uniform(dA, m, m, n)
     p.set_profile(2 * (1 << 0))
@@ -781,7 +781,7 @@ def test_tsqr_unequal_shards_agree_on_the_exchange(qr, oracle, heights, n, nb):
         tp.close()
 
 
-def test_tsqr_selfgather_back_to_back_and_unpipelined_agree(qr, oracle):
+def test_tsqr_selfgather_back_to_back_and_unpipelined_agree(qr, oracle, tmp_path):
     """One rank's complete step with its own factor in every rank slot (qr_tsqr_factor_selfgather_dev), issued back to back on four
     matrices without host synchronisation: every R is sqrt(P) times the R of ITS matrix; and the panel-pipelined schedule and the
     one-collective schedule (MI355XQR_TSQR_PIPE=0, child process) agree to rounding."""
@@ -811,7 +811,7 @@ def test_tsqr_selfgather_back_to_back_and_unpipelined_agree(qr, oracle):
             "A = torch.zeros((256, 32768), dtype=torch.float64, device='cuda'); R = torch.zeros((256, 256), dtype=torch.float64, device='cuda'); torch.cuda.synchronize()\n"
             "tp.local.fill_uniform(A, 32768, 32768, 256, seed=60); tp.sync(); tp.factor_selfgather(A, 32768, R); tp.sync()\n"
             "np.save(sys.argv[1], R.cpu().numpy().T)\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = "/tmp/tsqr_unpiped.npy"
+    path = str(tmp_path / "tsqr_unpiped.npy")
     subprocess.run([sys.executable, "-c", code, path], check=True, env=dict(os.environ, MI355XQR_TSQR_PIPE="0"))
     assert rel(oracle.sign_normalise(np.load(path)), outs[0]) < 1e-13
 
@@ -858,7 +858,7 @@ def test_tsqr_set_schedule_switches_between_the_two_exchange_forms_in_one_plan(q
     small.close()
 
 
-def test_tsqr_reserve_cus_masks_the_local_stream_and_changes_nothing_else(qr, oracle):
+def test_tsqr_reserve_cus_masks_the_local_stream_and_changes_nothing_else(qr, oracle, tmp_path):
     """MI355XQR_TSQR_RESERVE_CUS=16 (child process: the knob is read at plan creation; rounded up to 32 = one CU per shader engine): the
     local factorisation of a multi-rank plan runs on a stream masked to 224 compute units -- the full-width panel sizes its launches to
     that -- and the result is LAPACK's."""
@@ -869,9 +869,10 @@ def test_tsqr_reserve_cus_masks_the_local_stream_and_changes_nothing_else(qr, or
             "tp.local.fill_uniform(A, 65536, 65536, 256, seed=7); tp.sync(); A0 = A.cpu().numpy().T.copy()\n"
             "tp.factor_selfgather(A, 65536, R); tp.sync()\n"
             "np.save(sys.argv[1], R.cpu().numpy().T); np.save(sys.argv[2], A0)\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.run([sys.executable, "-c", code, "/tmp/tsqr_reserve_R.npy", "/tmp/tsqr_reserve_A.npy"], check=True,
+    fR, fA = str(tmp_path / "tsqr_reserve_R.npy"), str(tmp_path / "tsqr_reserve_A.npy")
+    subprocess.run([sys.executable, "-c", code, fR, fA], check=True,
                    env=dict(os.environ, MI355XQR_TSQR_RESERVE_CUS="16"), timeout=300)
-    R, A0 = np.load("/tmp/tsqr_reserve_R.npy"), np.load("/tmp/tsqr_reserve_A.npy")
+    R, A0 = np.load(fR), np.load(fA)
     ref = oracle.sign_normalise(np.linalg.qr(A0, mode="r")) * 2.0          # sqrt(P) with the rank's own factor in every slot
     assert rel(oracle.sign_normalise(np.triu(R)), ref) < 1e-13
 

@@ -71,12 +71,14 @@ def test_explicit_qr_restatement_bitwise_vs_golden(oracle, m, n, PR, PC, dtype):
 
 @pytest.mark.parametrize("m,n,PR,PC,dtype", CASES)
 def test_restatement_bitwise_vs_real_reference(oracle, m, n, PR, PC, dtype):
-    if oracle.ref_path(dtype, PR, PC) is None:
-        pytest.skip("oracle/_ref not built here (no /root/reference); golden fixtures cover this")
+    """Against the real reference where oracle/_ref was built; everywhere, against the digests of its outputs in the fixtures."""
     A = oracle.fill_rand(m, n, 12, dtype)
     F, tau, _ = oracle.mmqr(A, PR, PC)
-    Fr, taur = oracle.ref_mmqr(A, PR, PC)
-    assert np.array_equal(F, Fr) and np.array_equal(tau, taur)
+    g = load_golden(_name(m, n, PR, PC, dtype))
+    assert _sha(F) == str(g["sha_F"]) and _sha(tau) == str(g["sha_tau"])
+    if oracle.ref_path(dtype, PR, PC) is not None:
+        Fr, taur = oracle.ref_mmqr(A, PR, PC)
+        assert np.array_equal(F, Fr) and np.array_equal(tau, taur)
 
 
 def test_known_answers_from_survey(oracle):

@@ -134,7 +134,7 @@ def test_bench_under_torchrun_rccl_matches_single_gpu(workload, tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={P}",
                           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-                          "--gpus", str(P), "--steps", "3", "--warmup", "1", "--workload", workload, "--no-cpu-baseline"],
+                          "--gpus", str(P), "--steps", "3", "--warmup", "1", "--workload", workload, "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -157,7 +157,7 @@ def test_bench_bringup_two_ranks_on_one_gpu_through_the_c_abi_plan(tmp_path):
     env = dict(os.environ, BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", BENCH_WATCHDOG_S="120")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c4", "--no-cpu-baseline"],
+                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c4", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
