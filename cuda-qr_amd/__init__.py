@@ -39,11 +39,15 @@ except Exception:      # a host without torch: the binding works on raw device p
 lib = C.CDLL(LIB_PATH)
 
 QR_PROF_CLASSES = 4
+QR_E_ARG = -101
+QR_E_SINGULAR = -107
 PROF_NAMES = ("update_nn", "vta_tn", "panel", "vt_misc")
 
 
 class QRError(RuntimeError):
-    pass
+    def __init__(self, msg, status=0):
+        super().__init__(msg)
+        self.status = status
 
 
 class Profile(C.Structure):
@@ -107,6 +111,11 @@ _sig("qr_plan_create", C.c_int, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_i
 _sig("qr_plan_destroy", C.c_int, _vp)
 _sig("qr_geqrf_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("qr_applyq_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int)
+_sig("qr_build_t_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int)
+_sig("qr_ormqr_dev", C.c_int, _vp, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int)
+_sig("qr_solve_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
+_sig("qr_gels_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int)
+_sig("qr_lstsq", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -164,7 +173,7 @@ def strerror(rc):
 
 def check(rc, what=""):
     if rc != 0:
-        raise QRError(f"{what or 'mi355xqr'} failed: {strerror(rc)} ({rc})")
+        raise QRError(f"{what or 'mi355xqr'} failed: {strerror(rc)} ({rc})", rc)
 
 
 def exported_symbols():
@@ -327,6 +336,24 @@ def qr_thin_mgpu(A, nb=0, ngpu=1):
     return Q, R
 
 
+def lstsq(A, B):
+    """min ||A X - B|| for a full-rank m x n A (m >= n) through qr_lstsq: returns (X, resid), resid[j] = ||A x_j - b_j||.
+    A 1-D B is one column (X and resid then 1-D / a scalar).  Raises QRError (status QR_E_SINGULAR) when R has an exactly zero
+    diagonal entry."""
+    A = _f(A)
+    m, n = A.shape
+    B = np.asarray(B, dtype=np.float64)
+    vec = B.ndim == 1
+    B = _f(B.reshape(-1, 1) if vec else B)
+    if B.shape[0] != m:
+        raise QRError(f"lstsq: B has {B.shape[0]} rows, A has {m}", QR_E_ARG)
+    nrhs = B.shape[1]
+    X = np.empty((n, nrhs), order="F")
+    resid = np.empty(nrhs)
+    check(lib.qr_lstsq(_p(A), m, n, _p(B), nrhs, _p(X), _p(resid)), "qr_lstsq")
+    return (X[:, 0], resid[0]) if vec else (X, resid)
+
+
 def release_cached_plans():
     check(lib.qr_release_cached_plans(), "qr_release_cached_plans")
 
@@ -436,6 +463,23 @@ class Plan:
     def applyq(self, dA, m, n, lda, dtau, dC, ccols, ldc, identity_start):
         check(lib.qr_applyq_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dC), ccols, ldc,
                                 int(identity_start)), "qr_applyq_dev")
+
+    def build_t(self, dA, m, n, lda, dtau, dT, ldt):
+        """T of every outer block into dT (nb x n, ldt >= nb): qr_build_t_dev"""
+        check(lib.qr_build_t_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dT), ldt), "qr_build_t_dev")
+
+    def ormqr(self, trans, dA, m, n, lda, dtau, dC, nrhs, ldc, dT=None, ldt=0):
+        """dC <- Q^T dC (trans 'T') or Q dC ('N'); dT from build_t, or None: rebuilt panel by panel"""
+        check(lib.qr_ormqr_dev(self.h, trans.encode(), _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dT), ldt, _dptr(dC), nrhs, ldc),
+              "qr_ormqr_dev")
+
+    def solve_r(self, dA, n, lda, dB, nrhs, ldb):
+        """dB (n x nrhs) <- R^-1 dB, R = upper triangle of the factored dA"""
+        check(lib.qr_solve_r_dev(self.h, _dptr(dA), n, lda, _dptr(dB), nrhs, ldb), "qr_solve_r_dev")
+
+    def gels(self, dA, m, n, lda, dtau, dB, nrhs, ldb):
+        """dgels on the device: factors dA in place, dB rows 0..n-1 = X, rows n..m-1 = the tail of Q^T B"""
+        check(lib.qr_gels_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dB), nrhs, ldb), "qr_gels_dev")
 
     def extract_r(self, dA, m, n, lda, dR, rrows, ldr):
         check(lib.qr_extract_r_dev(self.h, _dptr(dA), m, n, lda, _dptr(dR), rrows, ldr), "qr_extract_r_dev")

@@ -170,6 +170,19 @@ int qrd_device_info(char* name, int name_len, int* cus, int* clock_khz, size_t* 
 int qrd_probe_mfma_f64(double* out3);
 int qrd_probe_copy(double* gbps);
 
+/* least-squares solve (qr_solve.hip, called from qr_solve.c only -- the stub device layer of the sanitizer builds does not have them).
+ * qrd_ormqr_skinny: Cs (mk x nrhs, ldc) <- (I - V op(T) V^T) Cs for the panel whose V is the unit lower trapezoid of Ak (mk x w, lda;
+ * read in place) and whose T is upper triangular (ldt); trans_t = 1: op(T) = T^T (Q^T C), 0: T (Q C).  ws: qrd_ormqr_skinny_ws doubles.
+ * Three launches, fixed-order sums.  -7: shape not taken (w > QRD_SOLVE_MAX_W).
+ * qrd_trsm_step: rows [row_lo, l1) of B -= R[.., x0:x1] B[x0:x1], then R[l0:l1, l0:l1] X = B[l0:l1] solved in place (l1 - l0 <= 64,
+ * x1 - x0 <= 64; x0 == x1: no update) */
+#define QRD_SOLVE_MAX_W 256
+int qrd_ormqr_skinny_blocks(int mk, int* rows_per_block);
+size_t qrd_ormqr_skinny_ws(int m, int w, int nrhs);    /* doubles of ws for every panel of a matrix of m rows */
+int qrd_ormqr_skinny(void* stream, const double* Ak, int lda, int mk, int w, const double* T, int ldt, int trans_t, double* Cs, int ldc,
+                     int nrhs, double* ws);
+int qrd_trsm_step(void* stream, const double* R, int lda, double* B, int ldb, int nrhs, int row_lo, int l0, int l1, int x0, int x1);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

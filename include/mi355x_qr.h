@@ -84,6 +84,7 @@ int explicitQR_legacy_status(double* A, double* tau, double* Q, double* R, int m
 #define QR_E_INTERNAL (-104)
 #define QR_E_STALL    (-105)  /* qr_plan_sync: a hand-off between the workgroups of a one-launch panel timed out; the factorisation is invalid */
 #define QR_E_REFUSED  (-106)  /* qr_plan_sync in latch mode (qr_plan_set_guard_mode): a full-width tall panel was refused; result invalid */
+#define QR_E_SINGULAR (-107)  /* qr_lstsq: R(i,i) == 0 exactly for some i (LAPACK dgels INFO > 0); no solution was computed */
 const char* qr_strerror(int status);
 
 /* Block sizes used by the drop-in entry points (outer compact-WY block nb: multiple of ib, <= 512, above 256 a multiple of 256;
@@ -283,6 +284,42 @@ int qr_device_info(char* arch, int arch_len, int* compute_units, int* clock_khz,
  * out3[1] = in-kernel shader clock (GHz) during that run, out3[2] = f64 VALU FMA TFLOP/s */
 int qr_probe_mfma_f64_tflops(double* out3);
 int qr_probe_copy_gbps(double* gbps);
+
+/* ---------------------------------------------------------------------------------------------
+ * 3. Solving with the factors: full-rank least squares min ||A X - B||, m >= n, fp64, column-major.
+ * No reference counterpart (the reference stops at Q and R, qr.c:330-438); the LAPACK routine each call corresponds to is named.
+ * Conventions of section 2: status return, queued on the plan's stream with no host wait, bad arguments (NULL plan or pointer, m < n,
+ * nrhs < 1, ld* < rows, sizes above the plan's, an unknown trans) return QR_E_ARG before anything touches a device.  The device calls
+ * do not look at R's diagonal: an exactly singular R gives inf / NaN in X.
+ * Workspace for the right-hand sides grows lazily with nrhs (as qr_applyq_dev's does): the first call at a larger nrhs allocates,
+ * and an allocation drains the plan and synchronises the device.
+ * ------------------------------------------------------------------------------------------- */
+
+/* LAPACK dlarft per outer block (dgeqrt's T layout): dT is nbp x n (ldt >= nbp, nbp = the plan's nb, qr_plan_info); columns [k, k+w)
+ * hold the w x w upper-triangular T of reflectors k .. k+w-1 (zeros below its diagonal), so that H_k .. H_{k+w-1} = I - V T V^T.
+ * Build once, apply many times. */
+int qr_build_t_dev(qr_plan* plan, const double* dA, int m, int n, int lda, const double* dtau, double* dT, int ldt);
+
+/* LAPACK dormqr (side 'L'): dC (m x nrhs, ldc) <- Q^T dC (trans 'T') or Q dC ('N'), Q = H_0 .. H_{n-1} from qr_geqrf_dev's factors.
+ * V is read in place from dA (unit diagonal implied, upper triangle ignored).  dT from qr_build_t_dev, or NULL: T is rebuilt panel
+ * by panel.  Up to 4 right-hand sides on tall matrices (m >= 16 n) a route of its own streams V twice per panel in place (no copy of V,
+ * fixed-order sums); otherwise the MFMA products of qr_applyq_dev.  Either way repeated calls give bitwise-equal results. */
+int qr_ormqr_dev(qr_plan* plan, char trans, const double* dA, int m, int n, int lda, const double* dtau, const double* dT, int ldt,
+                 double* dC, int nrhs, int ldc);
+
+/* LAPACK dtrtrs ('U', 'N', 'N'): dB (n x nrhs, ldb) <- R^{-1} dB, R = the upper triangle of the first n rows of the factored dA
+ * (non-unit diagonal; n <= the plan's n).  Blocked back substitution: 64-row diagonal blocks by substitution (no inverse is formed),
+ * one launch per block up to 64 right-hand sides, recursive halving with MFMA products above. */
+int qr_solve_r_dev(qr_plan* plan, const double* dA, int n, int lda, double* dB, int nrhs, int ldb);
+
+/* LAPACK dgels ('N', m >= n) on the device: factors dA in place (dtau: n doubles), overwrites dB (m x nrhs, ldb): rows 0..n-1 = X,
+ * rows n..m-1 = the last m-n entries of Q^T B, so ||dB[n:m, j]|| is the residual norm of column j. */
+int qr_gels_dev(qr_plan* plan, double* dA, int m, int n, int lda, double* dtau, double* dB, int nrhs, int ldb);
+
+/* LAPACK dgels on host pointers, A (m x n) and B (m x nrhs) untouched: X (n x nrhs, ld n), resid (nrhs doubles, may be NULL) =
+ * ||A x_j - b_j||_2 (from Q^T b_j).  Uses the plan cache of mmqr (qr_release_cached_plans).  Synchronous.  QR_E_SINGULAR when some
+ * R(i,i) == 0 exactly (LAPACK dgels INFO > 0); X and resid hold no solution then. */
+int qr_lstsq(const double* A, int m, int n, const double* B, int nrhs, double* X, double* resid);
 
 #ifdef __cplusplus
 }
