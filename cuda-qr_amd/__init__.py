@@ -116,6 +116,11 @@ _sig("qr_ormqr_dev", C.c_int, _vp, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _vp
 _sig("qr_solve_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gels_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int)
 _sig("qr_lstsq", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp)
+_ip = C.POINTER(C.c_int)
+_sig("qr_geqp3_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp)
+_sig("qr_rank_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _ip)
+_sig("qr_gelsp_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _ip)
+_sig("qr_lstsq_pivoted", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -354,6 +359,50 @@ def lstsq(A, B):
     return (X[:, 0], resid[0]) if vec else (X, resid)
 
 
+def lstsq_pivoted(A, B, rcond=None):
+    """min ||A X - B|| for an m x n A (m >= n) of any rank through qr_lstsq_pivoted: returns (X, resid, rank, jpvt).  X is the basic
+    solution: the rows jpvt[rank:] are zero.  rcond None: max(m, n) eps.  A 1-D B is one column (X and resid then 1-D / a scalar)."""
+    A = _f(A)
+    m, n = A.shape
+    B = np.asarray(B, dtype=np.float64)
+    vec = B.ndim == 1
+    B = _f(B.reshape(-1, 1) if vec else B)
+    if B.shape[0] != m:
+        raise QRError(f"lstsq_pivoted: B has {B.shape[0]} rows, A has {m}", QR_E_ARG)
+    nrhs = B.shape[1]
+    X = np.empty((n, nrhs), order="F")
+    resid = np.empty(nrhs)
+    jpvt = np.empty(max(n, 1), dtype=np.intc)
+    rank = C.c_int()
+    check(lib.qr_lstsq_pivoted(_p(A), m, n, _p(B), nrhs, -1.0 if rcond is None else float(rcond), _p(X), _p(resid), C.byref(rank),
+                               jpvt.ctypes.data_as(_ip)), "qr_lstsq_pivoted")
+    jpvt = jpvt[:n].astype(np.int64)
+    return (X[:, 0], resid[0], rank.value, jpvt) if vec else (X, resid, rank.value, jpvt)
+
+
+def qr_pivoted(A):
+    """A[:, jpvt] = Q R with decreasing |diag R| (qr_geqp3_dev): returns (Q m x n, R n x n, jpvt) for a host array."""
+    import torch
+    A = _f(A)
+    m, n = A.shape
+    if n < 1 or m < n:
+        raise QRError(f"qr_pivoted: {m} x {n} (m >= n >= 1 is required)", QR_E_ARG)
+    p = Plan(m, n)
+    try:
+        dA = to_device_colmajor(A)
+        dtau = torch.zeros(n, dtype=torch.float64, device="cuda")
+        dj = torch.zeros(n, dtype=torch.int32, device="cuda")
+        dQ = torch.zeros((n, m), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        p.geqp3(dA, m, n, m, dj, dtau)
+        p.applyq(dA, m, n, m, dtau, dQ, n, m, True)
+        p.sync()
+        F = from_device_colmajor(dA)
+        return from_device_colmajor(dQ), np.triu(F[:n]), dj.cpu().numpy().astype(np.int64)
+    finally:
+        p.close()
+
+
 def release_cached_plans():
     check(lib.qr_release_cached_plans(), "qr_release_cached_plans")
 
@@ -480,6 +529,23 @@ class Plan:
     def gels(self, dA, m, n, lda, dtau, dB, nrhs, ldb):
         """dgels on the device: factors dA in place, dB rows 0..n-1 = X, rows n..m-1 = the tail of Q^T B"""
         check(lib.qr_gels_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dB), nrhs, ldb), "qr_gels_dev")
+
+    def geqp3(self, dA, m, n, lda, djpvt, dtau):
+        """column-pivoted QR in place (factors laid out as geqrf's); djpvt: n int32 on the device, 0-based"""
+        check(lib.qr_geqp3_dev(self.h, _dptr(dA), m, n, lda, _dptr(djpvt), _dptr(dtau)), "qr_geqp3_dev")
+
+    def rank(self, dA, m, n, lda, rcond=None):
+        """numerical rank from geqp3's factors: |R(i,i)| > rcond |R(0,0)| (None: max(m, n) eps); synchronous"""
+        r = C.c_int()
+        check(lib.qr_rank_dev(self.h, _dptr(dA), m, n, lda, -1.0 if rcond is None else float(rcond), C.byref(r)), "qr_rank_dev")
+        return r.value
+
+    def gelsp(self, dA, m, n, lda, djpvt, dtau, dB, nrhs, ldb, rcond=None, dresid=None):
+        """rank-deficient least squares on the device (basic solution): dB rows 0..n-1 = X; returns the rank"""
+        r = C.c_int()
+        check(lib.qr_gelsp_dev(self.h, _dptr(dA), m, n, lda, _dptr(djpvt), _dptr(dtau), _dptr(dB), nrhs, ldb,
+                               -1.0 if rcond is None else float(rcond), _dptr(dresid), C.byref(r)), "qr_gelsp_dev")
+        return r.value
 
     def extract_r(self, dA, m, n, lda, dR, rrows, ldr):
         check(lib.qr_extract_r_dev(self.h, _dptr(dA), m, n, lda, _dptr(dR), rrows, ldr), "qr_extract_r_dev")

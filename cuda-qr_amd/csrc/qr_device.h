@@ -183,6 +183,30 @@ int qrd_ormqr_skinny(void* stream, const double* Ak, int lda, int mk, int w, con
                      int nrhs, double* ws);
 int qrd_trsm_step(void* stream, const double* R, int lda, double* B, int ldb, int nrhs, int row_lo, int l0, int l1, int x0, int x1);
 
+/* column-pivoted factorisation (qr_pivot.hip, called from qr_pivot.c only -- as above, the stub device layer does not have them).
+ * The workspace of a plan of n columns: qrd_pivot_ws_doubles(n) doubles and qrd_pivot_ws_ints(n) ints, bound by qrd_pivot_ws_bind.
+ *   F      ldf x QRD_PIVOT_NBP   LAPACK dlaqps' F of the current panel (row = column of the matrix)
+ *   FT     its trailing rows transposed, for the general product when the block update cannot go to qrd_gemm_nt
+ *   P      row-split partial sums of the gemv, vn1 / vn2 / flag: partial norms, their last exact values, columns to recompute
+ *   cval / cidx   one pivot candidate per 256 columns; pend: how many columns of the current panel are to be factored (INT_MAX: all)
+ * qrd_pivot_norms: exact norms of rows r0.. of the columns from c0 on (all != 0: every one, and jpvt = identity; else the flagged ones),
+ * candidates, pend reset.  qrd_pivot_column: column j of the panel at k0, three launches; a no-op once j >= *pend. */
+#define QRD_PIVOT_NBP 128
+#define QRD_PIVOT_MAX_SPLIT 64
+typedef struct qrd_pivot_ws {
+    double *F, *FT, *P, *vn1, *vn2, *npart, *alpha, *cval;
+    int *flag, *cidx, *pend;
+    int ldf;
+} qrd_pivot_ws;
+size_t qrd_pivot_ws_doubles(int n);
+size_t qrd_pivot_ws_ints(int n);
+void qrd_pivot_ws_bind(qrd_pivot_ws* w, int n, double* dbuf, int* ibuf);
+int qrd_pivot_norms(void* stream, const qrd_pivot_ws* w, const double* A, int lda, int m, int n, int r0, int c0, int all, int* jpvt);
+int qrd_pivot_column(void* stream, const qrd_pivot_ws* w, double* A, int lda, int m, int n, int k0, int j, int* jpvt, double* tau);
+/* S (n x nrhs, ld n): row jpvt[i] = row i of B for i < r, zero otherwise;  resid[j] = |B(r0:m, j)| */
+int qrd_pivot_scatter(void* stream, const double* B, int ldb, int n, int nrhs, int r, const int* jpvt, double* S);
+int qrd_pivot_resid(void* stream, const double* B, int ldb, int r0, int m, int nrhs, double* resid);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

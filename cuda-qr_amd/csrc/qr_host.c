@@ -523,6 +523,7 @@ int qr_plan_destroy(qr_plan* p)
     qrd_free(p->slabs); qrd_free(p->panel_ws); qrd_free(p->chol_ws); qrd_free(p->slabs_ep);
     qrd_free(p->pf_ws); qrd_free(p->pf_status); qrd_free(p->cq_ws); qrd_free(p->cq_status); qrd_free(p->padA); qrd_free(p->pad_tau);
     qrd_host_word_free(p->cq_hword);
+    qrd_free(p->pv_d); qrd_free(p->pv_i); qrd_free(p->pv_scatter);
     if (p->s_main) qrd_stream_destroy(p->s_main);
     free(p);
     return 0;

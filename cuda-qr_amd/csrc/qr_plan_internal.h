@@ -82,6 +82,11 @@ struct qr_plan {
     void* prof_stream;          /* stream of the open record */
     int* prof_cls;
     double *prof_flops, *prof_bytes;
+    /* column pivoting (qr_pivot.c): allocated on the first pivoted call, freed with the plan */
+    double* pv_d;               /* F, its transpose, gemv partials, partial norms, pivot candidates (qrd_pivot_ws_bind) */
+    int* pv_i;                  /* flags, candidate indices, the panel-length word */
+    double* pv_scatter;         /* n x nrhs: X in the caller's column order (qr_gelsp_dev) */
+    size_t pv_scatter_cap;
 };
 
 /* a cached plan of the host-pointer entry points and its device buffers (qr_host.c) */

@@ -10,7 +10,11 @@
  * `./qr_device m n --compare` adds the vendor line the reference prints under ENABLE_MAGMA (qr.cu:790-806, "MAGMA ran QR on ..."):
  * rocSOLVER's dgeqrf on the same matrix, resident in HBM.  rocSOLVER / rocBLAS are dlopen()ed by THIS tool only when the flag is
  * given: the library never links or loads them.
+ *
+ * `./qr_device m n --pivot` adds a line for the column-pivoted factorisation (qr_geqp3_dev, matrix resident in HBM): time, numerical
+ * rank and the residual ||A P - Q R||_F / ||A||_F with Q and the product formed on the device.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -57,10 +61,54 @@ static int vendor_line(const double* A, double* dA, double* dtau, int m, int n, 
     return 0;
 }
 
+/* qr_geqp3_dev on the resident matrix: time, rank, ||A P - Q R||_F / ||A||_F */
+static int pivot_line(qr_plan* p, const double* A, double* dA, double* dtau, int m, int n)
+{
+    const size_t cnt = (size_t) m * n;
+    int* djpvt = NULL;
+    double *dQ = NULL, *dR = NULL, *dC = NULL;
+    if (qr_device_malloc((void**) &djpvt, sizeof(int) * n) || qr_device_malloc((void**) &dQ, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dR, sizeof(double) * (size_t) n * n) || qr_device_malloc((void**) &dC, sizeof(double) * cnt)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dA, A, sizeof(double) * cnt)) { fprintf(stderr, "copy failed\n"); return 1; }
+        const double t0 = now();
+        if (qr_geqp3_dev(p, dA, m, n, m, djpvt, dtau) || qr_plan_sync(p)) { fprintf(stderr, "qr_geqp3_dev failed\n"); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    int rank = -1;
+    int* jpvt = malloc(sizeof(int) * n);
+    double* QR = malloc(sizeof(double) * cnt);
+    if (!jpvt || !QR || qr_rank_dev(p, dA, m, n, m, -1.0, &rank) || qr_applyq_dev(p, dA, m, n, m, dtau, dQ, n, m, 1) ||
+        qr_extract_r_dev(p, dA, m, n, m, dR, n, n) || qr_gemm_dev(p, 'N', m, n, n, 1.0, dQ, m, dR, n, 0.0, dC, m) || qr_plan_sync(p) ||
+        qr_copy_to_host(QR, dC, sizeof(double) * cnt) || qr_copy_to_host(jpvt, djpvt, sizeof(int) * n)) {
+        fprintf(stderr, "pivoted check failed\n");
+        return 1;
+    }
+    double num = 0.0, den = 0.0;
+    for (int j = 0; j < n; j++)
+        for (int i = 0; i < m; i++) {
+            const double a = A[(size_t) jpvt[j] * m + i], d = a - QR[(size_t) j * m + i];
+            num += d * d; den += a * a;
+        }
+    printf(" MMQR ran pivoted QR on %dx%d matrix in %f s (avg over %d)   [matrix resident in HBM, rank %d, residual %.2e]\n",
+           m, n, el / TRIALS, TRIALS, rank, sqrt(num / den));
+    free(jpvt); free(QR);
+    qr_device_free(djpvt); qr_device_free(dQ); qr_device_free(dR); qr_device_free(dC);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare]"); return 1; }
-    const int compare = argc > 3 && strcmp(argv[3], "--compare") == 0;
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot]"); return 1; }
+    int compare = 0, pivot = 0;
+    for (int i = 3; i < argc; i++) {
+        if (strcmp(argv[i], "--compare") == 0) compare = 1;
+        if (strcmp(argv[i], "--pivot") == 0) pivot = 1;
+    }
     const int m = atoi(argv[1]), n = atoi(argv[2]);
     if (m < 1 || n < 1 || m < n) { fprintf(stderr, "need m >= n >= 1\n"); return 1; }
     printf("Exact problem size: %dx%d\n", m, n);
@@ -104,6 +152,7 @@ int main(int argc, char** argv)
     printf(" MMQR ran QR on %dx%d matrix in %f s (avg over %d)   [matrix resident in HBM, %.1f GFLOP/s fp64]\n",
            m, n, el / TRIALS, TRIALS, flops / (el / TRIALS) / 1e9);
     if (compare && vendor_line(A, dA, dtau, m, n, flops)) return 1;
+    if (pivot && pivot_line(p, A, dA, dtau, m, n)) return 1;
     qr_device_free(dA); qr_device_free(dtau);
     qr_plan_destroy(p);
     free(A); free(RV);

@@ -321,6 +321,42 @@ int qr_gels_dev(qr_plan* plan, double* dA, int m, int n, int lda, double* dtau, 
  * R(i,i) == 0 exactly (LAPACK dgels INFO > 0); X and resid hold no solution then. */
 int qr_lstsq(const double* A, int m, int n, const double* B, int nrhs, double* X, double* resid);
 
+/* ---------------------------------------------------------------------------------------------
+ * 4. Column pivoting and rank: A P = Q R with |R(0,0)| >= |R(1,1)| >= ..., the numerical rank, and least squares for matrices whose
+ * columns are dependent or nearly so (what section 3 cannot answer).  No reference counterpart (the reference stops at Q and R,
+ * qr.c:330-438); the LAPACK routine each call corresponds to is named.  Conventions of sections 2 and 3: status return, work queued on
+ * the plan's stream, bad arguments (NULL plan or pointer, m < n, n < 1, nrhs < 1, ld* < rows, sizes above the plan's) return QR_E_ARG
+ * before anything touches a device.  Workspace hangs off the plan and is allocated on the first pivoted call (that call drains the plan).
+ * Half of the work of a pivoted factorisation is one matrix-vector product with the whole trailing matrix per column (memory-bound):
+ * measured: 11 to 25 times the cost of qr_geqrf_dev (README, "Pivoted QR").
+ * ------------------------------------------------------------------------------------------- */
+
+/* LAPACK dgeqp3 with every column free: A P = Q R.  dA (m x n, lda, m >= n) is overwritten exactly as qr_geqrf_dev overwrites it (R above,
+ * reflector tails below with an implied unit diagonal, dtau: n doubles), so qr_applyq_dev, qr_build_t_dev, qr_ormqr_dev, qr_solve_r_dev
+ * and qr_extract_r_dev work on the result unchanged.  djpvt: n ints on the device, 0-based: column j of A P is column djpvt[j] of the
+ * caller's A.  At step j the pivot is the remaining column of largest partial norm, lowest index on a tie; partial norms are downdated
+ * with LAPACK's safeguard (dlaqps), so a pivot can miss the true maximum by a relative sqrt(eps).
+ * Stream-ordered inside a panel of 32 columns; the host thread waits for the device once per panel (it reads how many columns the
+ * panel factored: a norm that has to be recomputed ends a panel early).  Repeated calls give bitwise-equal results. */
+int qr_geqp3_dev(qr_plan* plan, double* dA, int m, int n, int lda, int* djpvt, double* dtau);
+
+/* Numerical rank from the factors of qr_geqp3_dev: the number of i with |R(i,i)| > rcond * |R(0,0)|; rcond < 0 selects max(m, n) * DBL_EPSILON
+ * (m = the height that was factored).  Synchronous (drains the plan's streams, reads n doubles back).  A zero matrix has rank 0. */
+int qr_rank_dev(qr_plan* plan, const double* dA, int m, int n, int lda, double rcond, int* rank);
+
+/* Rank-deficient least squares, basic solution (what MATLAB's backslash returns; NOT the minimum-norm solution of LAPACK dgelsy):
+ * factors dA with pivoting, r = rank as above, X(djpvt[0..r), :) = R11^{-1} (Q^T B)(0..r, :), every other row of X = 0.
+ * On return rows 0..n-1 of dB (m x nrhs, ldb) hold X in the caller's column order; rows n..m-1 hold the last m-n entries of Q^T B as in
+ * qr_gels_dev; dresid (nrhs doubles on the device, may be NULL) = ||(Q^T b_j)(r..m)||_2 = ||A x_j - b_j||_2; *rank (host, may be NULL) = r.
+ * Waits for the device as qr_geqp3_dev does and once more to read r; everything else is stream-ordered. */
+int qr_gelsp_dev(qr_plan* plan, double* dA, int m, int n, int lda, int* djpvt, double* dtau, double* dB, int nrhs, int ldb,
+                 double rcond, double* dresid, int* rank);
+
+/* The same on host pointers, A (m x n) and B (m x nrhs) untouched (cf. qr_lstsq): X (n x nrhs, ld n), resid (nrhs doubles, may be NULL),
+ * rank (may be NULL), jpvt (n ints, may be NULL).  Never returns QR_E_SINGULAR: a zero matrix gives rank 0 and X = 0.  Uses the plan
+ * cache of mmqr (qr_release_cached_plans).  Synchronous. */
+int qr_lstsq_pivoted(const double* A, int m, int n, const double* B, int nrhs, double rcond, double* X, double* resid, int* rank, int* jpvt);
+
 #ifdef __cplusplus
 }
 #endif
