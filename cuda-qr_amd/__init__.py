@@ -121,6 +121,12 @@ _sig("qr_geqp3_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp)
 _sig("qr_rank_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _ip)
 _sig("qr_gelsp_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _ip)
 _sig("qr_lstsq_pivoted", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip, _ip)
+_sig("qr_solve_rt_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
+_sig("qr_minnorm_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int)
+_sig("qr_gels_t_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int)
+_sig("qr_transpose_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int)
+_sig("qr_gels_wide_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int)
+_sig("qr_lstsq_minnorm", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -167,6 +173,7 @@ _sig("qrd_leaf_update_gram", C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, 
 _sig("qrd_gemm_nt", C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp)
 if hasattr(lib, "qrd_gemm_nt4_ok"):        # (absent from libraries of earlier commits loaded for A/B runs through CUDA_QR_AMD_LIB)
     _sig("qrd_gemm_nt4_ok", C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int)
+_sig("qrd_transpose", C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int)
 _sig("qrd_copy_block", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int)
 _sig("qrd_init", C.c_int)
 _sig("qrd_device_sync", C.c_int)
@@ -380,6 +387,22 @@ def lstsq_pivoted(A, B, rcond=None):
     return (X[:, 0], resid[0], rank.value, jpvt) if vec else (X, resid, rank.value, jpvt)
 
 
+def lstsq_minnorm(A, B):
+    """The minimum-norm solution of A X = B for a full-rank wide m x n A (m <= n) through qr_lstsq_minnorm: returns X (n x nrhs).
+    A 1-D B is one column (X then 1-D).  Raises QRError (status QR_E_SINGULAR) when R of A^T has an exactly zero diagonal entry."""
+    A = _f(A)
+    m, n = A.shape
+    B = np.asarray(B, dtype=np.float64)
+    vec = B.ndim == 1
+    B = _f(B.reshape(-1, 1) if vec else B)
+    if B.shape[0] != m:
+        raise QRError(f"lstsq_minnorm: B has {B.shape[0]} rows, A has {m}", QR_E_ARG)
+    nrhs = B.shape[1]
+    X = np.empty((n, nrhs), order="F")
+    check(lib.qr_lstsq_minnorm(_p(A), m, n, _p(B), nrhs, _p(X)), "qr_lstsq_minnorm")
+    return X[:, 0] if vec else X
+
+
 def qr_pivoted(A):
     """A[:, jpvt] = Q R with decreasing |diag R| (qr_geqp3_dev): returns (Q m x n, R n x n, jpvt) for a host array."""
     import torch
@@ -529,6 +552,26 @@ class Plan:
     def gels(self, dA, m, n, lda, dtau, dB, nrhs, ldb):
         """dgels on the device: factors dA in place, dB rows 0..n-1 = X, rows n..m-1 = the tail of Q^T B"""
         check(lib.qr_gels_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dB), nrhs, ldb), "qr_gels_dev")
+
+    def solve_rt(self, dA, n, lda, dB, nrhs, ldb):
+        """dB (n x nrhs) <- R^-T dB, R = upper triangle of the factored dA"""
+        check(lib.qr_solve_rt_dev(self.h, _dptr(dA), n, lda, _dptr(dB), nrhs, ldb), "qr_solve_rt_dev")
+
+    def minnorm(self, dA, m, n, lda, dtau, dB, nrhs, ldb, dT=None, ldt=0):
+        """dB (m x nrhs; rows 0..n-1 = B) <- Q [R^-T B ; 0], the minimum-norm solution of A^T X = B, from existing factors"""
+        check(lib.qr_minnorm_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dT), ldt, _dptr(dB), nrhs, ldb), "qr_minnorm_dev")
+
+    def gels_t(self, dA, m, n, lda, dtau, dB, nrhs, ldb):
+        """dgels('T') on the device: factors dA (m x n, m >= n) in place, dB (m x nrhs; rows 0..n-1 = B) <- minimum-norm X of A^T X = B"""
+        check(lib.qr_gels_t_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dB), nrhs, ldb), "qr_gels_t_dev")
+
+    def transpose(self, dS, rows, cols, lds, dD, ldd):
+        """dD (cols x rows, ldd) = dS (rows x cols, lds)^T, out of place"""
+        check(lib.qr_transpose_dev(self.h, _dptr(dS), rows, cols, lds, _dptr(dD), ldd), "qr_transpose_dev")
+
+    def gels_wide(self, dA, m, n, lda, dF, ldf, dtau, dB, nrhs, ldb):
+        """dgels('N', m <= n) on a plan for n x m: dA (wide, untouched), dF (n x m) <- factors of A^T, dB (n x nrhs; rows 0..m-1 = B) <- X"""
+        check(lib.qr_gels_wide_dev(self.h, _dptr(dA), m, n, lda, _dptr(dF), ldf, _dptr(dtau), _dptr(dB), nrhs, ldb), "qr_gels_wide_dev")
 
     def geqp3(self, dA, m, n, lda, djpvt, dtau):
         """column-pivoted QR in place (factors laid out as geqrf's); djpvt: n int32 on the device, 0-based"""

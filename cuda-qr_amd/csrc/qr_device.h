@@ -183,6 +183,14 @@ int qrd_ormqr_skinny(void* stream, const double* Ak, int lda, int mk, int w, con
                      int nrhs, double* ws);
 int qrd_trsm_step(void* stream, const double* R, int lda, double* B, int ldb, int nrhs, int row_lo, int l0, int l1, int x0, int x1);
 
+/* minimum-norm solve (qr_minnorm.hip, called from qr_minnorm.c only -- as above, the stub device layer does not have them).
+ * qrd_trsm_t_step: the mirror of qrd_trsm_step for R^T X = B: rows [l0, row_hi) of B -= R[x0:x1, rows]^T B[x0:x1], then
+ * R[l0:l1, l0:l1]^T X = B[l0:l1] solved in place (l1 - l0 <= 64, x1 - x0 <= 64, x1 <= l0; x0 == x1: no update).
+ * qrd_transpose_tiled: D (cols x rows, ldd) = S (rows x cols, lds)^T on 64 x 64 tiles through LDS, both sides contiguous; any sizes,
+ * leading dimensions and bases (qrd_transpose above is the per-element kernel for the nb x nb blocks of T). */
+int qrd_trsm_t_step(void* stream, const double* R, int lda, double* B, int ldb, int nrhs, int row_hi, int l0, int l1, int x0, int x1);
+int qrd_transpose_tiled(void* stream, int rows, int cols, const double* S, int lds, double* D, int ldd);
+
 /* column-pivoted factorisation (qr_pivot.hip, called from qr_pivot.c only -- as above, the stub device layer does not have them).
  * The workspace of a plan of n columns: qrd_pivot_ws_doubles(n) doubles and qrd_pivot_ws_ints(n) ints, bound by qrd_pivot_ws_bind.
  *   F      ldf x QRD_PIVOT_NBP   LAPACK dlaqps' F of the current panel (row = column of the matrix)

@@ -13,6 +13,9 @@
  *
  * `./qr_device m n --pivot` adds a line for the column-pivoted factorisation (qr_geqp3_dev, matrix resident in HBM): time, numerical
  * rank and the residual ||A P - Q R||_F / ||A||_F with Q and the product formed on the device.
+ *
+ * `./qr_device m n --minnorm` reads m n as a WIDE shape (m <= n) and does nothing else: the minimum-norm solution of A x = b for one
+ * right-hand side (qr_gels_wide_dev, matrix resident in HBM, transpose included), time and ||A x - b|| / (||A||_F ||x||).
  */
 #include <math.h>
 #include <stdio.h>
@@ -101,15 +104,62 @@ static int pivot_line(qr_plan* p, const double* A, double* dA, double* dtau, int
     return 0;
 }
 
+/* the wide m x n system (m <= n), one right-hand side: qr_gels_wide_dev on the resident matrix */
+static int minnorm_main(int m, int n)
+{
+    if (m < 1 || m > n) { fprintf(stderr, "--minnorm needs 1 <= m <= n\n"); return 1; }
+    printf("Exact problem size: %dx%d (wide)\n", m, n);
+    const size_t cnt = (size_t) m * n;
+    double* A = malloc(sizeof(double) * cnt);
+    double* b = malloc(sizeof(double) * n);
+    double* x = malloc(sizeof(double) * n);
+    if (!A || !b || !x) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX;
+    for (int i = 0; i < n; i++) b[i] = i < m ? (double) rand() / RAND_MAX : 0.0;
+    qr_plan* p = NULL;
+    double *dA = NULL, *dF = NULL, *dtau = NULL, *dB = NULL;
+    if (qr_plan_create(&p, n, m, 0, 0) || qr_device_malloc((void**) &dA, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dF, sizeof(double) * cnt) || qr_device_malloc((void**) &dtau, sizeof(double) * m) ||
+        qr_device_malloc((void**) &dB, sizeof(double) * n) || qr_copy_to_device(dA, A, sizeof(double) * cnt)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dB, b, sizeof(double) * n)) { fprintf(stderr, "copy failed\n"); return 1; }
+        const double t0 = now();
+        if (qr_gels_wide_dev(p, dA, m, n, m, dF, n, dtau, dB, 1, n) || qr_plan_sync(p)) { fprintf(stderr, "qr_gels_wide_dev failed\n"); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(x, dB, sizeof(double) * n)) { fprintf(stderr, "copy failed\n"); return 1; }
+    double na = 0.0, nx = 0.0, nr = 0.0;
+    for (size_t i = 0; i < cnt; i++) na += A[i] * A[i];
+    for (int j = 0; j < n; j++) nx += x[j] * x[j];
+    for (int i = 0; i < m; i++) {
+        double r = -b[i];
+        for (int j = 0; j < n; j++) r += A[(size_t) j * m + i] * x[j];
+        nr += r * r;
+    }
+    printf(" MMQR ran minimum-norm solve on %dx%d matrix in %f s (avg over %d)   [matrix resident in HBM, ||A x - b|| / (||A|| ||x||) = %.2e]\n",
+           m, n, el / TRIALS, TRIALS, sqrt(nr) / (sqrt(na) * sqrt(nx)));
+    qr_device_free(dA); qr_device_free(dF); qr_device_free(dtau); qr_device_free(dB);
+    qr_plan_destroy(p);
+    free(A); free(b); free(x);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot]"); return 1; }
-    int compare = 0, pivot = 0;
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n)"); return 1; }
+    int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "--compare") == 0) compare = 1;
         if (strcmp(argv[i], "--pivot") == 0) pivot = 1;
+        if (strcmp(argv[i], "--minnorm") == 0) minnorm = 1;
     }
     const int m = atoi(argv[1]), n = atoi(argv[2]);
+    if (minnorm) return minnorm_main(m, n);
     if (m < 1 || n < 1 || m < n) { fprintf(stderr, "need m >= n >= 1\n"); return 1; }
     printf("Exact problem size: %dx%d\n", m, n);
     char arch[64]; int cus = 0, khz = 0; size_t hbm = 0;

@@ -357,6 +357,51 @@ int qr_gelsp_dev(qr_plan* plan, double* dA, int m, int n, int lda, int* djpvt, d
  * cache of mmqr (qr_release_cached_plans).  Synchronous. */
 int qr_lstsq_pivoted(const double* A, int m, int n, const double* B, int nrhs, double rcond, double* X, double* resid, int* rank, int* jpvt);
 
+/* ---------------------------------------------------------------------------------------------
+ * 5. Minimum-norm solutions: underdetermined and transposed systems.  With A = Q R (m x n, m >= n, full rank) the system A^T X = B has
+ * infinitely many solutions when m > n; the one of least norm is X = Q [R^{-T} B ; 0].  A wide system is the same thing read the other
+ * way: factor its transpose.  No reference counterpart (the reference stops at Q and R, qr.c:330-438); the LAPACK routine each call
+ * corresponds to is named.  Conventions of sections 2 to 4: status return, work queued on the plan's stream with no host wait, bad
+ * arguments (NULL plan or pointer, nrhs < 1, ld* < rows, sizes above the plan's, the wrong one of m < n / m > n) return QR_E_ARG before
+ * anything touches a device; the device calls do not look at R's diagonal (an exactly singular R gives inf / NaN in X); repeated calls
+ * give bitwise-equal results (fixed-order sums, no floating-point atomics).  The entry points of section 3 keep answering QR_E_ARG
+ * for m < n: everything here is a symbol of its own.
+ * ------------------------------------------------------------------------------------------- */
+
+/* LAPACK dtrtrs ('U', 'T', 'N'): dB (n x nrhs, ldb) <- R^{-T} dB, R = the upper triangle of the first n rows of the factored dA
+ * (non-unit diagonal; n <= the plan's n).  Blocked forward substitution, the mirror of qr_solve_r_dev: 64-row diagonal blocks by
+ * substitution (no inverse is formed), one launch per block up to 64 right-hand sides -- the launch updates every row below the block
+ * just solved and solves the next one --, recursive halving with MFMA products above. */
+int qr_solve_rt_dev(qr_plan* plan, const double* dA, int n, int lda, double* dB, int nrhs, int ldb);
+
+/* Minimum-norm solution of A^T X = B from factors that already exist (qr_geqrf_dev's or qr_geqp3_dev's layout; for the latter the
+ * system solved is (A P)^T X = B): factor once, solve many.  dB is m x nrhs (ldb >= m): rows 0..n-1 hold B on entry, rows n..m-1 are
+ * ignored; on return dB = X = Q [R^{-T} B ; 0].  dT from qr_build_t_dev, or NULL, as in qr_ormqr_dev.  LAPACK: the dtrtrs + dormqr
+ * half of dgels ('T'). */
+int qr_minnorm_dev(qr_plan* plan, const double* dA, int m, int n, int lda, const double* dtau, const double* dT, int ldt, double* dB,
+                   int nrhs, int ldb);
+
+/* LAPACK dgels ('T', m >= n) on the device: factors dA in place (dtau: n doubles), then qr_minnorm_dev: dB (m x nrhs, ldb), rows
+ * 0..n-1 = B on entry, = the minimum-norm X of A^T X = B on return. */
+int qr_gels_t_dev(qr_plan* plan, double* dA, int m, int n, int lda, double* dtau, double* dB, int nrhs, int ldb);
+
+/* dD (cols x rows, ldd >= cols) = dS (rows x cols, lds >= rows)^T, out of place, any sizes (not bounded by the plan's), leading
+ * dimensions and bases; nothing outside the cols x rows block of dD is written.  64 x 64 tiles through LDS: the read and the write are
+ * both contiguous.  No LAPACK counterpart (BLAS extensions call it omatcopy 'T'). */
+int qr_transpose_dev(qr_plan* plan, const double* dS, int rows, int cols, int lds, double* dD, int ldd);
+
+/* LAPACK dgels ('N', m <= n) for a wide column-major dA (m x n, lda >= m), which is not modified: the minimum-norm X of A X = B.
+ * The plan is one for the TRANSPOSED shape: plan rows >= n, plan columns >= m.  dF (n x m, ldf >= n) receives the factors of A^T in
+ * qr_geqrf_dev's layout and dtau its m scalars, so that qr_minnorm_dev(plan, dF, n, m, ldf, dtau, ..) solves again.  dB is n x nrhs
+ * (ldb >= n): rows 0..m-1 hold B on entry; on return it holds X. */
+int qr_gels_wide_dev(qr_plan* plan, const double* dA, int m, int n, int lda, double* dF, int ldf, double* dtau, double* dB, int nrhs,
+                     int ldb);
+
+/* LAPACK dgels ('N', m <= n) on host pointers, A (m x n) and B (m x nrhs, ld m) untouched: X (n x nrhs, ld n) = the minimum-norm
+ * solution.  A is uploaded as it is and transposed on the device.  Uses the plan cache of mmqr, keyed on the transposed shape
+ * (qr_release_cached_plans).  Synchronous.  QR_E_SINGULAR when some R(i,i) == 0 exactly (X holds no solution then); QR_E_ARG when m > n. */
+int qr_lstsq_minnorm(const double* A, int m, int n, const double* B, int nrhs, double* X);
+
 #ifdef __cplusplus
 }
 #endif
