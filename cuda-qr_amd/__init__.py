@@ -127,6 +127,17 @@ _sig("qr_gels_t_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.
 _sig("qr_transpose_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int)
 _sig("qr_gels_wide_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int)
 _sig("qr_lstsq_minnorm", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp)
+_sig("qr_tpqrt_max_rows", C.c_int)
+_sig("qr_tpqrt_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int)
+_sig("qr_tpmqrt_dev", C.c_int, _vp, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
+_sig("qr_lsacc_create", C.c_int, C.POINTER(_vp), _vp, C.c_int, C.c_int)
+_sig("qr_lsacc_push_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int)
+_sig("qr_lsacc_rows", C.c_int, _vp, C.POINTER(C.c_longlong))
+_sig("qr_lsacc_factor_dev", C.c_int, _vp, C.POINTER(_vp), _ip, C.POINTER(_vp), _ip)
+_sig("qr_lsacc_solve_dev", C.c_int, _vp, _vp, C.c_int, _vp)
+_sig("qr_lsacc_reset", C.c_int, _vp)
+_sig("qr_lsacc_destroy", C.c_int, _vp)
+_sig("qr_lstsq_chunked", C.c_int, _dp, C.c_longlong, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -403,6 +414,32 @@ def lstsq_minnorm(A, B):
     return X[:, 0] if vec else X
 
 
+def lstsq_chunked(A, B, chunk_rows):
+    """min ||A X - B|| for a full-rank m x n A through qr_lstsq_chunked: chunk_rows rows at a time are uploaded and folded into an
+    accumulator (device memory bounded by the chunk): returns (X, resid) as lstsq does.  Raises QRError (status QR_E_SINGULAR) when R
+    has an exactly zero diagonal entry or A has fewer rows than columns."""
+    A = _f(A)
+    m, n = A.shape
+    B = np.asarray(B, dtype=np.float64)
+    vec = B.ndim == 1
+    B = _f(B.reshape(-1, 1) if vec else B)
+    if B.shape[0] != m:
+        raise QRError(f"lstsq_chunked: B has {B.shape[0]} rows, A has {m}", QR_E_ARG)
+    nrhs = B.shape[1]
+    X = np.empty((n, nrhs), order="F")
+    resid = np.empty(nrhs)
+    check(lib.qr_lstsq_chunked(_p(A), m, n, m, _p(B), nrhs, m, int(chunk_rows), _p(X), _p(resid)), "qr_lstsq_chunked")
+    return (X[:, 0], resid[0]) if vec else (X, resid)
+
+
+def tpqrt_max_rows():
+    """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
+    return lib.qr_tpqrt_max_rows()
+
+
+TPQRT_PANEL = 32        # QR_TPQRT_PANEL: rows of the block T that Plan.tpqrt writes
+
+
 def qr_pivoted(A):
     """A[:, jpvt] = Q R with decreasing |diag R| (qr_geqp3_dev): returns (Q m x n, R n x n, jpvt) for a host array."""
     import torch
@@ -573,6 +610,15 @@ class Plan:
         """dgels('N', m <= n) on a plan for n x m: dA (wide, untouched), dF (n x m) <- factors of A^T, dB (n x nrhs; rows 0..m-1 = B) <- X"""
         check(lib.qr_gels_wide_dev(self.h, _dptr(dA), m, n, lda, _dptr(dF), ldf, _dptr(dtau), _dptr(dB), nrhs, ldb), "qr_gels_wide_dev")
 
+    def tpqrt(self, dR, n, ldr, dB, p, ldb, dT, ldt):
+        """dtpqrt (L = 0): [R ; B] = Q' [R' ; 0] in place: dR (n x n upper triangle) <- R', dB (p x n) <- V, dT (32 x n) <- the block T"""
+        check(lib.qr_tpqrt_dev(self.h, _dptr(dR), n, ldr, _dptr(dB), p, ldb, _dptr(dT), ldt), "qr_tpqrt_dev")
+
+    def tpmqrt(self, trans, dV, p, n, ldv, dT, ldt, dC1, ldc1, dC2, ldc2, nrhs):
+        """dtpmqrt (side 'L'): [C1 ; C2] <- Q'^T [C1 ; C2] (trans 'T') or Q' [C1 ; C2] ('N') with dV, dT from tpqrt"""
+        check(lib.qr_tpmqrt_dev(self.h, trans.encode(), _dptr(dV), p, n, ldv, _dptr(dT), ldt, _dptr(dC1), ldc1, _dptr(dC2), ldc2, nrhs),
+              "qr_tpmqrt_dev")
+
     def geqp3(self, dA, m, n, lda, djpvt, dtau):
         """column-pivoted QR in place (factors laid out as geqrf's); djpvt: n int32 on the device, 0-based"""
         check(lib.qr_geqp3_dev(self.h, _dptr(dA), m, n, lda, _dptr(djpvt), _dptr(dtau)), "qr_geqp3_dev")
@@ -631,6 +677,56 @@ class Plan:
         check(lib.qr_plan_get_profile(self.h, C.byref(pr)), "qr_plan_get_profile")
         return {PROF_NAMES[c]: {"ms": pr.ms[c], "flops": pr.flops[c], "bytes": pr.bytes[c],
                                 "launches": pr.launches[c]} for c in range(QR_PROF_CLASSES)}
+
+
+class LsAccumulator:
+    """qr_lsacc wrapper: least squares over rows pushed chunk by chunk (R, Q^T b and the residual sums of squares stay on the device).
+    The plan must stay open for as long as the accumulator is used."""
+
+    def __init__(self, plan, n, nrhs):
+        self.h = None
+        h = _vp()
+        check(lib.qr_lsacc_create(C.byref(h), plan.h, n, nrhs), "qr_lsacc_create")
+        self.h, self.plan, self.n, self.nrhs = h, plan, n, nrhs
+
+    def close(self):
+        if self.h and lib is not None and self.plan.h:
+            lib.qr_lsacc_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def push(self, dA, p, lda, dB, ldb):
+        """fold in p rows [dA | dB]; both buffers are workspace and hold nothing defined afterwards"""
+        check(lib.qr_lsacc_push_dev(self.h, _dptr(dA), p, lda, _dptr(dB), ldb), "qr_lsacc_push_dev")
+
+    def rows(self):
+        r = C.c_longlong()
+        check(lib.qr_lsacc_rows(self.h, C.byref(r)), "qr_lsacc_rows")
+        return r.value
+
+    def factor(self):
+        """(dR, ldr, dZ, ldz): device addresses (ints) of the n x n R and the n x nrhs Z = (Q^T b)(0:n)"""
+        r, z, ldr, ldz = _vp(), _vp(), C.c_int(), C.c_int()
+        check(lib.qr_lsacc_factor_dev(self.h, C.byref(r), C.byref(ldr), C.byref(z), C.byref(ldz)), "qr_lsacc_factor_dev")
+        return r.value, ldr.value, z.value, ldz.value
+
+    def factor_host(self):
+        """numpy copies (R n x n, Z n x nrhs) of the current state; synchronises the plan"""
+        r, ldr, z, ldz = self.factor()
+        self.plan.sync()
+        R = np.empty((self.n, ldr), order="C")          # the column-major image: row c = column c
+        Z = np.empty((self.nrhs, ldz), order="C")
+        check(lib.qr_copy_to_host(R.ctypes.data, r, R.nbytes), "qr_copy_to_host")
+        check(lib.qr_copy_to_host(Z.ctypes.data, z, Z.nbytes), "qr_copy_to_host")
+        return np.asfortranarray(R[:, :self.n].T), np.asfortranarray(Z[:, :self.n].T)
+
+    def solve(self, dX, ldx, dresid=None):
+        """dX (n x nrhs) <- the least-squares solution of everything pushed so far; dresid (nrhs) <- the residual norms"""
+        check(lib.qr_lsacc_solve_dev(self.h, _dptr(dX), ldx, _dptr(dresid)), "qr_lsacc_solve_dev")
+
+    def reset(self):
+        check(lib.qr_lsacc_reset(self.h), "qr_lsacc_reset")
 
 
 class TsqrPlan:

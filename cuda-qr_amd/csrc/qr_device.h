@@ -191,6 +191,20 @@ int qrd_trsm_step(void* stream, const double* R, int lda, double* B, int ldb, in
 int qrd_trsm_t_step(void* stream, const double* R, int lda, double* B, int ldb, int nrhs, int row_hi, int l0, int l1, int x0, int x1);
 int qrd_transpose_tiled(void* stream, int rows, int cols, const double* S, int lds, double* D, int ldd);
 
+/* row-append update (qr_update.hip, called from qr_update.c only -- as above, the stub device layer does not have them).
+ * qrd_tp_panel: [Rkk (w x w upper triangle, ldr; its strict lower triangle is neither read nor written) ; Bk (p x w, ldb)] factored in
+ * place by one workgroup: R' over the triangle, V over Bk, the w x w T (zeros below its diagonal) to Tk (ldt); w <= QRD_TP_W, p <= QRD_TP_MAXROWS.
+ * qrd_tp_apply: W = op(Tk) (C1k + Vk^T C2), C1k -= W, C2 -= Vk W over ncols columns (C1k: w rows; C2: p rows), one workgroup per 32
+ * columns; trans_t = 1: op(T) = T^T (Q^T C), 0: T (Q C).
+ * qrd_tp_colssq_add: acc[c] += |X(0:rows, c)|^2 in a fixed order;  qrd_tp_sqrt: out[i] = sqrt(in[i]).  -7: shape not taken */
+#define QRD_TP_W 32
+#define QRD_TP_MAXROWS 256
+int qrd_tp_panel(void* stream, double* Rkk, int ldr, double* Bk, int ldb, int p, int w, double* Tk, int ldt);
+int qrd_tp_apply(void* stream, int trans_t, const double* Vk, int ldv, int p, int w, const double* Tk, int ldt, double* C1k, int ldc1,
+                 double* C2, int ldc2, int ncols);
+int qrd_tp_colssq_add(void* stream, const double* X, int ldx, int rows, int cols, double* acc);
+int qrd_tp_sqrt(void* stream, const double* in, double* out, int n);
+
 /* column-pivoted factorisation (qr_pivot.hip, called from qr_pivot.c only -- as above, the stub device layer does not have them).
  * The workspace of a plan of n columns: qrd_pivot_ws_doubles(n) doubles and qrd_pivot_ws_ints(n) ints, bound by qrd_pivot_ws_bind.
  *   F      ldf x QRD_PIVOT_NBP   LAPACK dlaqps' F of the current panel (row = column of the matrix)

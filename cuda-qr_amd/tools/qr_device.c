@@ -16,6 +16,10 @@
  *
  * `./qr_device m n --minnorm` reads m n as a WIDE shape (m <= n) and does nothing else: the minimum-norm solution of A x = b for one
  * right-hand side (qr_gels_wide_dev, matrix resident in HBM, transpose included), time and ||A x - b|| / (||A||_F ||x||).
+ *
+ * `./qr_device m n --append [chunk_rows]` does nothing else either: the rows of the matrix are pushed into a least-squares accumulator
+ * chunk_rows at a time (default 4096; qr_lsacc_push_dev, chunks resident in HBM), beside one qr_gels_dev on the whole matrix: both
+ * times, the factor error ||R_acc^T R_acc - R^T R||_F / ||R^T R||_F and the solution error ||x_acc - x||_2 / ||x||_2.
  */
 #include <math.h>
 #include <stdio.h>
@@ -149,10 +153,86 @@ static int minnorm_main(int m, int n)
     return 0;
 }
 
+/* R^T R of the n x n upper triangle in the leading rows of F (ld ldf) into G (n x n) */
+static void gram_of_triangle(const double* F, int ldf, int n, double* G)
+{
+    for (int j = 0; j < n; j++)
+        for (int i = 0; i <= j; i++) {
+            double s = 0.0;
+            for (int k = 0; k <= i; k++) s += F[(size_t) i * ldf + k] * F[(size_t) j * ldf + k];
+            G[(size_t) j * n + i] = G[(size_t) i * n + j] = s;
+        }
+}
+
+/* m x n, one right-hand side: the rows pushed chunk by chunk into a qr_lsacc against one qr_gels_dev on the whole matrix */
+static int append_main(int m, int n, int chunk)
+{
+    if (n < 1 || m < n || chunk < 1) { fprintf(stderr, "--append needs m >= n >= 1 and chunk_rows >= 1\n"); return 1; }
+    if (chunk > m) chunk = m;
+    printf("Exact problem size: %dx%d, pushed %d rows at a time\n", m, n, chunk);
+    const size_t cnt = (size_t) m * n, nn = (size_t) n * n;
+    double *A = malloc(sizeof(double) * cnt), *b = malloc(sizeof(double) * m), *F = malloc(sizeof(double) * cnt), *xb = malloc(sizeof(double) * m);
+    double *Ra = malloc(sizeof(double) * nn), *xa = malloc(sizeof(double) * n), *G0 = malloc(sizeof(double) * nn), *G1 = malloc(sizeof(double) * nn);
+    double *Ac = malloc(sizeof(double) * (size_t) chunk * n);
+    if (!A || !b || !F || !xb || !Ra || !xa || !G0 || !G1 || !Ac) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    for (int i = 0; i < m; i++) b[i] = (double) rand() / RAND_MAX - 0.5;
+    const int pm = chunk > n ? chunk : n;
+    qr_plan *p = NULL, *pc = NULL;
+    qr_lsacc* acc = NULL;
+    double *dA = NULL, *dtau = NULL, *dB = NULL, *dAc = NULL, *dBc = NULL, *dX = NULL;
+    if (qr_plan_create(&p, m, n, 0, 0) || qr_plan_create(&pc, pm, n, 0, 0) || qr_lsacc_create(&acc, pc, n, 1) ||
+        qr_device_malloc((void**) &dA, sizeof(double) * cnt) || qr_device_malloc((void**) &dtau, sizeof(double) * n) ||
+        qr_device_malloc((void**) &dB, sizeof(double) * m) || qr_device_malloc((void**) &dAc, sizeof(double) * (size_t) chunk * n) ||
+        qr_device_malloc((void**) &dBc, sizeof(double) * chunk) || qr_device_malloc((void**) &dX, sizeof(double) * n)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0, ela = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dA, A, sizeof(double) * cnt) || qr_copy_to_device(dB, b, sizeof(double) * m)) { fprintf(stderr, "copy failed\n"); return 1; }
+        const double t0 = now();
+        if (qr_gels_dev(p, dA, m, n, m, dtau, dB, 1, m) || qr_plan_sync(p)) { fprintf(stderr, "qr_gels_dev failed\n"); return 1; }
+        if (t >= 0) el += now() - t0;
+        if (qr_lsacc_reset(acc) || qr_plan_sync(pc)) { fprintf(stderr, "qr_lsacc_reset failed\n"); return 1; }
+        for (int r = 0; r < m; r += chunk) {          /* the uploads are not timed: the chunks count as resident, like the matrix above */
+            const int h = m - r < chunk ? m - r : chunk;
+            for (int j = 0; j < n; j++) memcpy(Ac + (size_t) j * h, A + (size_t) j * m + r, sizeof(double) * h);
+            if (qr_copy_to_device(dAc, Ac, sizeof(double) * (size_t) h * n) || qr_copy_to_device(dBc, b + r, sizeof(double) * h)) { fprintf(stderr, "copy failed\n"); return 1; }
+            const double t1 = now();
+            if (qr_lsacc_push_dev(acc, dAc, h, h, dBc, h) || qr_plan_sync(pc)) { fprintf(stderr, "qr_lsacc_push_dev failed\n"); return 1; }
+            if (t >= 0) ela += now() - t1;
+        }
+        const double t2 = now();
+        if (qr_lsacc_solve_dev(acc, dX, n, NULL) || qr_plan_sync(pc)) { fprintf(stderr, "qr_lsacc_solve_dev failed\n"); return 1; }
+        if (t >= 0) ela += now() - t2;
+    }
+    const double* dR = NULL;
+    int ldr = 0;
+    if (qr_lsacc_factor_dev(acc, &dR, &ldr, NULL, NULL) || qr_copy_to_host(Ra, dR, sizeof(double) * nn) || qr_copy_to_host(xa, dX, sizeof(double) * n) ||
+        qr_copy_to_host(F, dA, sizeof(double) * cnt) || qr_copy_to_host(xb, dB, sizeof(double) * m)) { fprintf(stderr, "copy failed\n"); return 1; }
+    gram_of_triangle(F, m, n, G0);
+    gram_of_triangle(Ra, ldr, n, G1);
+    double gn = 0.0, gd = 0.0, xn = 0.0, xd = 0.0;
+    for (size_t i = 0; i < nn; i++) { gn += (G1[i] - G0[i]) * (G1[i] - G0[i]); gd += G0[i] * G0[i]; }
+    for (int i = 0; i < n; i++) { xn += (xa[i] - xb[i]) * (xa[i] - xb[i]); xd += xb[i] * xb[i]; }
+    printf(" MMQR ran least squares on %dx%d matrix in %f s (avg over %d)   [qr_gels_dev, matrix resident in HBM]\n", m, n, el / TRIALS, TRIALS);
+    printf(" MMQR ran the same in chunks of %d rows in %f s (avg over %d)   [accumulator; factor error %.2e, solution error %.2e]\n",
+           chunk, ela / TRIALS, TRIALS, sqrt(gn / gd), sqrt(xn / xd));
+    qr_lsacc_destroy(acc);
+    qr_device_free(dA); qr_device_free(dtau); qr_device_free(dB); qr_device_free(dAc); qr_device_free(dBc); qr_device_free(dX);
+    qr_plan_destroy(p); qr_plan_destroy(pc);
+    free(A); free(b); free(F); free(xb); free(Ra); free(xa); free(G0); free(G1); free(Ac);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n)"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
+    for (int i = 3; i < argc; i++)
+        if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "--compare") == 0) compare = 1;
         if (strcmp(argv[i], "--pivot") == 0) pivot = 1;

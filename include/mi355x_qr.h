@@ -402,6 +402,76 @@ int qr_gels_wide_dev(qr_plan* plan, const double* dA, int m, int n, int lda, dou
  * (qr_release_cached_plans).  Synchronous.  QR_E_SINGULAR when some R(i,i) == 0 exactly (X holds no solution then); QR_E_ARG when m > n. */
 int qr_lstsq_minnorm(const double* A, int m, int n, const double* B, int nrhs, double* X);
 
+/* ---------------------------------------------------------------------------------------------
+ * 6. Row-append updating and streaming least squares: rows that arrive in pieces.  The building block is the QR factorisation of a
+ * triangle stacked on a block of new rows, [R ; B] = Q' [R' ; 0] -- the step TSQR is made of --, which costs 2 p n^2 flops for p new
+ * rows instead of the 2 (n + p) n^2 of a dense factorisation of the stacked matrix, never touches the zero half of R and works for any
+ * p >= 1.  No reference counterpart (the reference factors one resident matrix, qr.c:55-313); the LAPACK routine each call corresponds
+ * to is named.  Conventions of sections 2 to 5: status return, work queued on the plan's stream with no host wait unless stated
+ * otherwise, bad arguments (NULL plan or pointer, a size below 1 or above its limit, ld* < rows, an unknown trans) return QR_E_ARG
+ * before anything touches a device; repeated calls give bitwise-equal results (fixed-order sums, no floating-point atomics); fp64,
+ * column-major.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Reflectors are blocked in panels of QR_TPQRT_PANEL columns (a constant of the implementation); a block of new rows handed to one
+ * call has at most qr_tpqrt_max_rows() = 256 rows: the update kernel keeps the 256 x 32 reflector panel AND a 256 x 32 slab of the
+ * matrix it updates in one workgroup's LDS (2 x 64.5 KiB, + 25 KiB of T and W tiles, of the CU's 160 KiB), so that the slab is read
+ * from memory once and written once; 512 rows would leave no room for the slab.  Taller blocks go through the accumulator below or are
+ * fed block by block: qr_tpqrt_dev answers QR_E_ARG above the limit. */
+#define QR_TPQRT_PANEL 32
+int qr_tpqrt_max_rows(void);
+
+/* LAPACK dtpqrt (M = p, N = n, L = 0).  On entry dR (ldr >= n) is n x n upper triangular -- its strict lower triangle is neither read
+ * nor written -- and dB (ldb >= p) is p x n, 1 <= p <= qr_tpqrt_max_rows(), n <= the plan's n.  On return dR holds R' with
+ * [R ; B] = Q' [R' ; 0], dB holds V: reflector j is [e_j ; V(:, j)], the identity on top is implied; dT (QR_TPQRT_PANEL x n,
+ * ldt >= QR_TPQRT_PANEL) is the block T in qr_build_t_dev's layout at a panel width of QR_TPQRT_PANEL: columns [k, k + w) hold the
+ * w x w upper-triangular T of reflectors k .. k + w - 1, zeros below its diagonal.
+ * LAPACK dlarfg per column: beta = -sign(R(j,j)) hypot(R(j,j), |B(:,j)|); a column of B that is exactly zero gives tau = 0 and leaves
+ * everything untouched, so R = 0 on entry is legal (that is how an accumulation starts); exact zeros in B stay exact zeros, so a caller
+ * may hand over an upper-triangular block with explicit zeros and get V of the same shape.  (dlarfg's rescaling of subnormal columns
+ * is not reproduced.)  Two launches per QR_TPQRT_PANEL columns. */
+int qr_tpqrt_dev(qr_plan* plan, double* dR, int n, int ldr, double* dB, int p, int ldb, double* dT, int ldt);
+
+/* LAPACK dtpmqrt (side 'L', L = 0): [C1 ; C2] <- Q'^T [C1 ; C2] (trans 'T') or Q' [C1 ; C2] ('N') with dV, dT from qr_tpqrt_dev;
+ * dC1 is n x nrhs (ldc1 >= n), dC2 is p x nrhs (ldc2 >= p).  One launch per panel. */
+int qr_tpmqrt_dev(qr_plan* plan, char trans, const double* dV, int p, int n, int ldv, const double* dT, int ldt,
+                  double* dC1, int ldc1, double* dC2, int ldc2, int nrhs);
+
+/* Least-squares accumulator for min ||A x_j - b_j|| over rows that arrive chunk by chunk: it keeps R (n x n), Z = the first n entries
+ * of Q^T b (n x nrhs) and one sum of squares per right-hand side, all zero at the start; n <= the plan's n.  The plan must outlive it.
+ *   qr_lsacc_push_dev    folds in p >= 1 rows [dA | dB] (dA: p x n, lda >= p; dB: p x nrhs, ldb >= p) and uses both buffers as workspace:
+ *                        they hold nothing defined on return.  The route follows from the shape by construction, not from a measured rule:
+ *                          p >= n (p <= the plan's m): qr_geqrf_dev on the chunk, qr_ormqr_dev('T') on its right-hand sides, rows n .. p
+ *                             of the result into the sums of squares, then the chunk's triangle is merged in row blocks of at most
+ *                             qr_tpqrt_max_rows() rows: block i of an upper-triangular matrix is zero left of column i * rows, so its
+ *                             merge works on R[i rows:, i rows:] only -- the zero columns are skipped, not multiplied;
+ *                          p < n: qr_tpqrt_dev directly on the rows, in row blocks of at most qr_tpqrt_max_rows(), one after the other.
+ *                        In both routes the right-hand sides ride along (qr_tpmqrt_dev 'T'), and what is left in their new rows goes
+ *                        into the sums of squares.
+ *   qr_lsacc_rows        rows pushed so far (host bookkeeping, no device access)
+ *   qr_lsacc_factor_dev  the device addresses of R (upper triangular, zeros below) and Z and their leading dimensions (any may be NULL);
+ *                        they stay valid, and change with every push, until the accumulator is destroyed
+ *   qr_lsacc_solve_dev   dX (n x nrhs, ldx >= n) = R^{-1} Z through qr_solve_r_dev; dresid (nrhs doubles on the device, may be NULL) =
+ *                        the square roots of the sums of squares = ||A x_j - b_j||_2.  The state is untouched: pushing may continue.
+ *                        Like qr_gels_dev it does not look at R's diagonal.
+ *   qr_lsacc_reset       back to the empty state;  qr_lsacc_destroy waits for the plan's stream, then frees. */
+typedef struct qr_lsacc qr_lsacc;
+int qr_lsacc_create(qr_lsacc** acc, qr_plan* plan, int n, int nrhs);
+int qr_lsacc_push_dev(qr_lsacc* acc, double* dA, int p, int lda, double* dB, int ldb);
+int qr_lsacc_rows(qr_lsacc* acc, long long* rows);
+int qr_lsacc_factor_dev(qr_lsacc* acc, const double** dR, int* ldr, const double** dZ, int* ldz);
+int qr_lsacc_solve_dev(qr_lsacc* acc, double* dX, int ldx, double* dresid);
+int qr_lsacc_reset(qr_lsacc* acc);
+int qr_lsacc_destroy(qr_lsacc* acc);
+
+/* Least squares on host pointers for a matrix taller than the device should hold: A (m x n, lda >= m) and B (m x nrhs, ldb >= m) are
+ * untouched; chunk_rows rows at a time (at most m) are uploaded and pushed into an accumulator, so device memory is bounded by the
+ * chunk, not by m.  X (n x nrhs, ld n), resid (nrhs doubles, may be NULL) as in qr_lstsq.  Uses the plan cache of mmqr, keyed on
+ * (max(chunk_rows, n), n) (qr_release_cached_plans).  Synchronous.  QR_E_SINGULAR when some R(i,i) == 0 exactly, and when m < n
+ * (X holds no solution then); QR_E_ARG for chunk_rows < 1. */
+int qr_lstsq_chunked(const double* A, long long m, int n, int lda, const double* B, int nrhs, int ldb,
+                     int chunk_rows, double* X, double* resid);
+
 #ifdef __cplusplus
 }
 #endif
