@@ -41,6 +41,9 @@ lib = C.CDLL(LIB_PATH)
 QR_PROF_CLASSES = 4
 QR_E_ARG = -101
 QR_E_SINGULAR = -107
+QR_E_NOCONV = -108
+JSVD_BLOCK = 32         # QR_JSVD_BLOCK: the column-block width of the Jacobi schedule
+JSVD_MAX_SWEEPS = 30    # QR_JSVD_MAX_SWEEPS
 PROF_NAMES = ("update_nn", "vta_tn", "panel", "vt_misc")
 
 
@@ -138,6 +141,14 @@ _sig("qr_lsacc_solve_dev", C.c_int, _vp, _vp, C.c_int, _vp)
 _sig("qr_lsacc_reset", C.c_int, _vp)
 _sig("qr_lsacc_destroy", C.c_int, _vp)
 _sig("qr_lstsq_chunked", C.c_int, _dp, C.c_longlong, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp)
+_sig("qr_jsvd_rounds", C.c_int, C.c_int, _ip, _ip)
+_sig("qr_jsvd_round_pairs", C.c_int, C.c_int, C.c_int, _ip, C.c_int)
+_sig("qr_gesvj_dev", C.c_int, _vp, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _ip)
+_sig("qr_gesvd_dev", C.c_int, _vp, C.c_char, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _ip)
+_sig("qr_cond_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _dp)
+_sig("qr_gelss_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _ip)
+_sig("qr_svd", C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp)
+_sig("qr_lstsq_svd", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip, _dp)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -440,6 +451,77 @@ def tpqrt_max_rows():
 TPQRT_PANEL = 32        # QR_TPQRT_PANEL: rows of the block T that Plan.tpqrt writes
 
 
+def jsvd_rounds(n):
+    """(nblk, rounds) of the Jacobi tournament over the column blocks of an n-column matrix (qr_jsvd_rounds; no device)"""
+    nblk, rounds = C.c_int(), C.c_int()
+    check(lib.qr_jsvd_rounds(n, C.byref(nblk), C.byref(rounds)), "qr_jsvd_rounds")
+    return nblk.value, rounds.value
+
+
+def jsvd_round_pairs(n, round):
+    """[(p, q)] the block pairs of one round, exactly what the device code runs (qr_jsvd_round_pairs; no device)"""
+    nblk, _ = jsvd_rounds(n)
+    cap = max(1, nblk // 2)
+    buf = (C.c_int * (2 * cap))()
+    cnt = lib.qr_jsvd_round_pairs(n, round, buf, cap)
+    if cnt < 0:
+        check(cnt, "qr_jsvd_round_pairs")
+    return [(buf[2 * i], buf[2 * i + 1]) for i in range(cnt)]
+
+
+def _tall(A, what):
+    A = _f(A)
+    if A.ndim != 2 or A.shape[1] < 1 or A.shape[0] < A.shape[1]:
+        raise QRError(f"{what}: {A.shape} (a 2-D array with m >= n >= 1 is required; transpose a wide one)", QR_E_ARG)
+    return A
+
+
+def svd(A, compute_uv=True):
+    """The SVD of a tall m x n A (m >= n) through qr_svd: (U m x n, S descending, V n x n) with A = U diag(S) V^T -- V, not numpy's V^T --
+    or S alone with compute_uv False."""
+    A = _tall(A, "svd")
+    m, n = A.shape
+    S = np.empty(n)
+    if not compute_uv:
+        check(lib.qr_svd(_p(A), m, n, _p(S), None, None), "qr_svd")
+        return S
+    U = np.empty((m, n), order="F")
+    V = np.empty((n, n), order="F")
+    check(lib.qr_svd(_p(A), m, n, _p(S), _p(U), _p(V)), "qr_svd")
+    return U, S, V
+
+
+def svdvals(A):
+    """the singular values of a tall A, descending"""
+    return svd(A, compute_uv=False)
+
+
+def cond(A):
+    """the 2-norm condition number sigma_max / sigma_min of a tall A; inf when sigma_min == 0"""
+    S = svdvals(A)
+    return float(S[0] / S[-1]) if S[-1] > 0.0 else float("inf")
+
+
+def lstsq_svd(A, B, rcond=None):
+    """The minimum-norm solution of min ||A X - B|| for an m x n A (m >= n) of any rank through qr_lstsq_svd (LAPACK dgelss):
+    returns (X, resid, rank, S).  rcond None: max(m, n) eps.  A 1-D B is one column (X and resid then 1-D / a scalar)."""
+    A = _f(A)
+    m, n = A.shape
+    B = np.asarray(B, dtype=np.float64)
+    vec = B.ndim == 1
+    B = _f(B.reshape(-1, 1) if vec else B)
+    if B.shape[0] != m:
+        raise QRError(f"lstsq_svd: B has {B.shape[0]} rows, A has {m}", QR_E_ARG)
+    nrhs = B.shape[1]
+    X = np.empty((max(n, 1), nrhs), order="F")
+    resid = np.empty(nrhs)
+    S = np.empty(max(n, 1))
+    rank = C.c_int()
+    check(lib.qr_lstsq_svd(_p(A), m, n, _p(B), nrhs, -1.0 if rcond is None else float(rcond), _p(X), _p(resid), C.byref(rank), _p(S)),
+          "qr_lstsq_svd")
+    return (X[:, 0], resid[0], rank.value, S) if vec else (X, resid, rank.value, S)
+
+
 def qr_pivoted(A):
     """A[:, jpvt] = Q R with decreasing |diag R| (qr_geqp3_dev): returns (Q m x n, R n x n, jpvt) for a host array."""
     import torch
@@ -618,6 +700,34 @@ class Plan:
         """dtpmqrt (side 'L'): [C1 ; C2] <- Q'^T [C1 ; C2] (trans 'T') or Q' [C1 ; C2] ('N') with dV, dT from tpqrt"""
         check(lib.qr_tpmqrt_dev(self.h, trans.encode(), _dptr(dV), p, n, ldv, _dptr(dT), ldt, _dptr(dC1), ldc1, _dptr(dC2), ldc2, nrhs),
               "qr_tpmqrt_dev")
+
+    def gesvj(self, jobv, dG, r, n, ldg, dS, dV=None, ldv=0):
+        """dgesvj on the device: dG (r x n) <- the left singular vectors, dS <- the values (descending), dV (jobv 'V') <- the right ones;
+        returns the sweeps used.  Raises QRError (status QR_E_NOCONV) after JSVD_MAX_SWEEPS sweeps."""
+        sw = C.c_int()
+        check(lib.qr_gesvj_dev(self.h, jobv.encode(), _dptr(dG), r, n, ldg, _dptr(dS), _dptr(dV), ldv, C.byref(sw)), "qr_gesvj_dev")
+        return sw.value
+
+    def gesvd(self, jobu, jobv, dA, m, n, lda, dtau, dS, dU=None, ldu=0, dV=None, ldv=0):
+        """the tall SVD on the device: factors dA in place (geqrf's layout), dS <- the values, dU (m x n, jobu 'U'), dV (n x n, jobv 'V');
+        returns the sweeps used"""
+        sw = C.c_int()
+        check(lib.qr_gesvd_dev(self.h, jobu.encode(), jobv.encode(), _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dS), _dptr(dU), ldu,
+                               _dptr(dV), ldv, C.byref(sw)), "qr_gesvd_dev")
+        return sw.value
+
+    def cond(self, dA, m, n, lda, dtau):
+        """sigma_max / sigma_min (inf for a singular matrix); factors dA in place; synchronous"""
+        c = C.c_double()
+        check(lib.qr_cond_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), C.byref(c)), "qr_cond_dev")
+        return c.value
+
+    def gelss(self, dA, m, n, lda, dtau, dB, nrhs, ldb, dS, rcond=None):
+        """dgelss on the device (minimum-norm solution, any rank): dB rows 0..n-1 = X, dS <- the singular values; returns the rank"""
+        r = C.c_int()
+        check(lib.qr_gelss_dev(self.h, _dptr(dA), m, n, lda, _dptr(dtau), _dptr(dB), nrhs, ldb, -1.0 if rcond is None else float(rcond),
+                               _dptr(dS), C.byref(r)), "qr_gelss_dev")
+        return r.value
 
     def geqp3(self, dA, m, n, lda, djpvt, dtau):
         """column-pivoted QR in place (factors laid out as geqrf's); djpvt: n int32 on the device, 0-based"""

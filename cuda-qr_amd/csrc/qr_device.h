@@ -205,6 +205,26 @@ int qrd_tp_apply(void* stream, int trans_t, const double* Vk, int ldv, int p, in
 int qrd_tp_colssq_add(void* stream, const double* X, int ldx, int rows, int cols, double* acc);
 int qrd_tp_sqrt(void* stream, const double* in, double* out, int n);
 
+/* one-sided block Jacobi SVD (qr_svd.hip, called from qr_svd.c only -- as above, the stub device layer does not have them).
+ * qrd_jsvd_round: one round of the tournament, one workgroup per block pair: pairs = 2 npairs device ints (p, q) in units of
+ * QRD_JSVD_BLOCK columns (p == q: the self-pair of a one-block matrix); G is r x n (ldg), V (n x n, ldv) receives the same rotations
+ * (NULL: none accumulated); slots[i] = the measure max |s_ij| / sqrt(s_ii s_jj) pair i met BEFORE it rotated; a pair at or below tol
+ * is left alone.  qrd_jsvd_fold: word[0] = the maximum of count slots.
+ * qrd_jsvd_colnorms: out[c] = |G(:, c)|.  perm (n device ints): column j of the result is column perm[j] & (QRD_JSVD_LEAD - 1) of the
+ * input; bit QRD_JSVD_LEAD marks the first column of each cycle (qrd_jsvd_permute walks the cycles in place; qrd_jsvd_gather: values).
+ * qrd_jsvd_normalise: G(:, c) /= sig[c] where sig[c] > 0.  qrd_jsvd_pinv_scale: T2[i, :] = T1[i, :] / sig[i] where sig[i] > rc sig[0],
+ * else 0 (both n x nrhs, ld n).  qrd_jsvd_rt: W (n x n, ldw) = R^T of the factored A, zeros above the diagonal.  -7: bad shape */
+#define QRD_JSVD_BLOCK 32
+#define QRD_JSVD_LEAD 0x40000000
+int qrd_jsvd_round(void* stream, double* G, int ldg, int r, int n, double* V, int ldv, const int* pairs, int npairs, double tol, double* slots);
+int qrd_jsvd_fold(void* stream, const double* slots, int count, double* word);
+int qrd_jsvd_colnorms(void* stream, const double* G, int ldg, int r, int n, double* out);
+int qrd_jsvd_gather(void* stream, const double* sig, const int* perm, double* out, int n);
+int qrd_jsvd_permute(void* stream, double* M, int ld, int rows, int n, const int* perm);
+int qrd_jsvd_normalise(void* stream, double* G, int ldg, int r, int n, const double* sig);
+int qrd_jsvd_pinv_scale(void* stream, const double* T1, double* T2, int n, int nrhs, const double* sig, double rc);
+int qrd_jsvd_rt(void* stream, const double* A, int lda, int n, double* W, int ldw);
+
 /* column-pivoted factorisation (qr_pivot.hip, called from qr_pivot.c only -- as above, the stub device layer does not have them).
  * The workspace of a plan of n columns: qrd_pivot_ws_doubles(n) doubles and qrd_pivot_ws_ints(n) ints, bound by qrd_pivot_ws_bind.
  *   F      ldf x QRD_PIVOT_NBP   LAPACK dlaqps' F of the current panel (row = column of the matrix)

@@ -87,6 +87,12 @@ struct qr_plan {
     int* pv_i;                  /* flags, candidate indices, the panel-length word */
     double* pv_scatter;         /* n x nrhs: X in the caller's column order (qr_gelsp_dev) */
     size_t pv_scatter_cap;
+    /* Jacobi SVD (qr_svd.c): allocated on the first call of header section 7 (sized for the plan's n), freed with the plan */
+    double* sv_d;               /* R^T (n x n), the accumulated rotations (n x n), unsorted values (n), one slot per block pair, the sweep's word */
+    int* sv_i;                  /* the block pairs of a sweep, the sort permutation */
+    int* sv_h;                  /* host image of sv_i (the copies are asynchronous: it has to outlive the call) */
+    double* sv_t;               /* 2 x (n x nrhs): Z^T c and its scaled copy (qr_gelss_dev) */
+    size_t sv_t_cap;
 };
 
 /* a cached plan of the host-pointer entry points and its device buffers (qr_host.c) */

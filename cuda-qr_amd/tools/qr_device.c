@@ -20,6 +20,10 @@
  * `./qr_device m n --append [chunk_rows]` does nothing else either: the rows of the matrix are pushed into a least-squares accumulator
  * chunk_rows at a time (default 4096; qr_lsacc_push_dev, chunks resident in HBM), beside one qr_gels_dev on the whole matrix: both
  * times, the factor error ||R_acc^T R_acc - R^T R||_F / ||R^T R||_F and the solution error ||x_acc - x||_2 / ||x||_2.
+ *
+ * `./qr_device m n --svd` does nothing else either: the SVD of the matrix (qr_gesvd_dev with U and V, matrix resident in HBM): time,
+ * sigma_max, sigma_min, the Jacobi sweeps, ||A - U S V^T||_F / ||A||_F and the two orthogonality errors ||U^T U - I||_F, ||V^T V - I||_F
+ * (products formed on the host).
  */
 #include <math.h>
 #include <stdio.h>
@@ -227,12 +231,75 @@ static int append_main(int m, int n, int chunk)
     return 0;
 }
 
+/* ||X^T X - I||_F of the rows x cols column-major X */
+static double orth_err(const double* X, int rows, int cols)
+{
+    double e = 0.0;
+    for (int j = 0; j < cols; j++)
+        for (int i = 0; i <= j; i++) {
+            double s = i == j ? -1.0 : 0.0;
+            for (int k = 0; k < rows; k++) s += X[(size_t) i * rows + k] * X[(size_t) j * rows + k];
+            e += (i == j ? 1.0 : 2.0) * s * s;
+        }
+    return sqrt(e);
+}
+
+/* m x n, m >= n: qr_gesvd_dev with both sets of vectors on the resident matrix */
+static int svd_main(int m, int n)
+{
+    if (n < 1 || m < n) { fprintf(stderr, "--svd needs m >= n >= 1\n"); return 1; }
+    printf("Exact problem size: %dx%d\n", m, n);
+    const size_t cnt = (size_t) m * n, nn = (size_t) n * n;
+    double *A = malloc(sizeof(double) * cnt), *U = malloc(sizeof(double) * cnt), *V = malloc(sizeof(double) * nn), *S = malloc(sizeof(double) * n);
+    if (!A || !U || !V || !S) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    qr_plan* p = NULL;
+    double *dA = NULL, *dtau = NULL, *dS = NULL, *dU = NULL, *dV = NULL;
+    if (qr_plan_create(&p, m, n, 0, 0) || qr_device_malloc((void**) &dA, sizeof(double) * cnt) || qr_device_malloc((void**) &dtau, sizeof(double) * n) ||
+        qr_device_malloc((void**) &dS, sizeof(double) * n) || qr_device_malloc((void**) &dU, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dV, sizeof(double) * nn)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0;
+    int sweeps = 0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dA, A, sizeof(double) * cnt)) { fprintf(stderr, "copy failed\n"); return 1; }
+        const double t0 = now();
+        const int rc = qr_gesvd_dev(p, 'U', 'V', dA, m, n, m, dtau, dS, dU, m, dV, n, &sweeps);
+        if (rc || qr_plan_sync(p)) { fprintf(stderr, "qr_gesvd_dev failed: %s\n", qr_strerror(rc)); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(U, dU, sizeof(double) * cnt) || qr_copy_to_host(V, dV, sizeof(double) * nn) || qr_copy_to_host(S, dS, sizeof(double) * n)) {
+        fprintf(stderr, "copy failed\n");
+        return 1;
+    }
+    double na = 0.0, nr = 0.0;
+    for (int j = 0; j < n; j++)
+        for (int i = 0; i < m; i++) {
+            double s = -A[(size_t) j * m + i];
+            for (int k = 0; k < n; k++) s += U[(size_t) k * m + i] * S[k] * V[(size_t) k * n + j];
+            nr += s * s;
+            na += A[(size_t) j * m + i] * A[(size_t) j * m + i];
+        }
+    printf(" MMQR ran SVD on %dx%d matrix in %f s (avg over %d)   [matrix resident in HBM, U and V formed]\n", m, n, el / TRIALS, TRIALS);
+    printf(" sigma_max = %.6e  sigma_min = %.6e  sweeps = %d\n", S[0], S[n - 1], sweeps);
+    printf(" ||A - U S V^T|| / ||A|| = %.2e   ||U^T U - I|| = %.2e   ||V^T V - I|| = %.2e\n", sqrt(nr / na), orth_err(U, m, n), orth_err(V, n, n));
+    qr_device_free(dA); qr_device_free(dtau); qr_device_free(dS); qr_device_free(dU); qr_device_free(dV);
+    qr_plan_destroy(p);
+    free(A); free(U); free(V); free(S);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
+    for (int i = 3; i < argc; i++)
+        if (strcmp(argv[i], "--svd") == 0) return svd_main(atoi(argv[1]), atoi(argv[2]));
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "--compare") == 0) compare = 1;
         if (strcmp(argv[i], "--pivot") == 0) pivot = 1;

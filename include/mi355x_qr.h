@@ -85,6 +85,7 @@ int explicitQR_legacy_status(double* A, double* tau, double* Q, double* R, int m
 #define QR_E_STALL    (-105)  /* qr_plan_sync: a hand-off between the workgroups of a one-launch panel timed out; the factorisation is invalid */
 #define QR_E_REFUSED  (-106)  /* qr_plan_sync in latch mode (qr_plan_set_guard_mode): a full-width tall panel was refused; result invalid */
 #define QR_E_SINGULAR (-107)  /* qr_lstsq: R(i,i) == 0 exactly for some i (LAPACK dgels INFO > 0); no solution was computed */
+#define QR_E_NOCONV   (-108)  /* section 7: the Jacobi iteration did not reach its threshold in QR_JSVD_MAX_SWEEPS sweeps; results are not to be used */
 const char* qr_strerror(int status);
 
 /* Block sizes used by the drop-in entry points (outer compact-WY block nb: multiple of ib, <= 512, above 256 a multiple of 256;
@@ -471,6 +472,82 @@ int qr_lsacc_destroy(qr_lsacc* acc);
  * (X holds no solution then); QR_E_ARG for chunk_rows < 1. */
 int qr_lstsq_chunked(const double* A, long long m, int n, int lda, const double* B, int nrhs, int ldb,
                      int chunk_rows, double* X, double* resid);
+
+/* ---------------------------------------------------------------------------------------------
+ * 7. Singular values, SVD and minimum-norm least squares of rank-deficient systems.  With A = Q R (m x n, m >= n) and the SVD of the
+ * n x n triangle, R = W S Z^T, A = (Q W) S Z^T: the tall part is qr_geqrf_dev, the small dense part a one-sided block Jacobi SVD (LAPACK
+ * dgesvj; dgejsv takes the same QR-then-Jacobi route).  The iteration runs on R^T, not R: the rows of a triangular factor are far
+ * closer to orthogonal than its columns (an n = 96 matrix of condition 1e10 took 4 sweeps on R^T against 15 on R in a CPU emulation of
+ * this algorithm; dgejsv makes the same choice).  No reference counterpart (the reference stops at Q and R, qr.c:330-438); the LAPACK
+ * routine each call corresponds to is named.  Conventions of sections 3 to 6: status return, work queued on the plan's stream, bad
+ * arguments (NULL plan or pointer, sizes below 1 or above the plan's, ld* < rows, an unknown job letter) return QR_E_ARG before anything
+ * touches a device; repeated calls give bitwise-equal results (fixed-order sums, exact maxima, no floating-point atomics); fp64,
+ * column-major.  Workspace hangs off the plan and is allocated on the first call of this section (that call drains the plan).
+ *
+ * The iteration: the columns are cut into blocks of QR_JSVD_BLOCK; a sweep is a round-robin tournament over the blocks (below), one
+ * launch per round, one workgroup per block pair: Gram matrix of the pair's 64 columns on MFMA tiles, cyclic Jacobi rotations of the
+ * smaller angle on that 64 x 64 matrix in LDS, the accumulated 64 x 64 rotation applied to the columns on MFMA tiles.  A pair whose
+ * columns are already orthogonal to tol = sqrt(rows) * DBL_EPSILON (LAPACK's threshold: max |g_i . g_j| / (|g_i| |g_j|)) is left alone;
+ * the iteration ends with the first sweep in which every pair was (so an input with orthogonal columns takes one sweep, and the count
+ * reported includes that last, idle sweep).  No workgroup waits for another; the sweep loop is bounded by QR_JSVD_MAX_SWEEPS on the host.
+ * Accuracy is that of the QR itself: values to n eps of the largest, norm-wise.  Two columns whose norms differ by more than a factor
+ * DBL_EPSILON are not rotated against each other (the smaller one cannot change the larger by an ulp): that is what lets an exactly
+ * rank-deficient input converge, and it is why values below eps times their neighbours' carry no relative accuracy.  Column norms are plain sums of squares (dgesvj's
+ * rescaling against over- and underflow is not reproduced).
+ * Out of scope: m < n (transpose with qr_transpose_dev and swap the roles of U and V); a qr_geqp3_dev-preconditioned variant for high
+ * RELATIVE accuracy of tiny singular values (dgejsv's); a multi-GPU driver (it follows from qr_tsqr_factor_dev's R and is a later change).
+ * ------------------------------------------------------------------------------------------- */
+#define QR_JSVD_BLOCK 32
+#define QR_JSVD_MAX_SWEEPS 30      /* LAPACK dgesvj's limit */
+
+/* The tournament the device code runs, on the host (no device is touched): nblk = ceil(n / QR_JSVD_BLOCK) column blocks, `rounds` rounds
+ * per sweep -- nblk for an odd nblk (one block sits out each round), nblk - 1 for an even one; a sweep contains every unordered pair of
+ * distinct blocks exactly once and no block twice in a round.  nblk == 1: one round with the self-pair (0, 0).
+ * qr_jsvd_round_pairs writes round `round`'s pairs as 2 ints each (p, q), p < q, into pairs (room for cap pairs) and returns their
+ * count; QR_E_ARG for n < 1, a round outside [0, rounds), NULL pairs or too small a cap.  (Circle method: with N = the odd one of
+ * nblk, nblk - 1, round s pairs (s + k) mod N with (s - k) mod N, k = 1 .. (N - 1) / 2; an even nblk adds (s, nblk - 1).) */
+int qr_jsvd_rounds(int n, int* nblk, int* rounds);
+int qr_jsvd_round_pairs(int n, int round, int* pairs, int cap);
+
+/* LAPACK dgesvj (r >= n; r <= the plan's m, n <= the plan's n).  On entry dG (ldg >= r) is any r x n matrix.  On return dS[0..n) holds
+ * the singular values in descending order and the columns of dG the left singular vectors, of unit norm; a column whose singular value
+ * is exactly 0 is an exact zero column.  jobv 'V': dV (n x n, ldv >= n) holds the right singular vectors, G_in = dG diag(dS) dV^T;
+ * jobv 'N': dV may be NULL, no rotations are accumulated (dS is bitwise the same).  *sweeps (host, may be NULL) = sweeps used.
+ * The host thread waits once per sweep (it reads the sweep's convergence word) and once more for the descending sort: n doubles come
+ * back, n ints go out; the sort is stable, ties keep column order.  Everything else is stream-ordered.  QR_E_NOCONV after
+ * QR_JSVD_MAX_SWEEPS sweeps.  Nothing outside the r x n / n x n / n extents is written. */
+int qr_gesvj_dev(qr_plan* plan, char jobv, double* dG, int r, int n, int ldg, double* dS, double* dV, int ldv, int* sweeps);
+
+/* The SVD of a tall matrix (LAPACK dgesvd / dgejsv with jobs 'S' / 'N'), m >= n: qr_geqrf_dev on dA (the factors stay in dA, dtau as
+ * usual: qr_ormqr_dev etc. keep working on them), R^T into an n x n workspace, qr_gesvj_dev's iteration on it.  dS: n values, descending.
+ * jobv 'V': dV (n x n, ldv >= n) = the right singular vectors of A (the normalised columns of the iterate); 'N': dV may be NULL.
+ * jobu 'U': dU (m x n, ldu >= m) = Q [Z ; 0] with Z the accumulated rotations, through qr_ormqr_dev ('N'); 'N': dU may be NULL.
+ * A = dU diag(dS) dV^T.  jobu = jobv = 'N': values only, no accumulation and no Q apply (dS is bitwise the same).  A column of dU
+ * that belongs to a zero singular value is a unit vector orthogonal to the others, as in LAPACK.  Host waits as qr_gesvj_dev. */
+int qr_gesvd_dev(qr_plan* plan, char jobu, char jobv, double* dA, int m, int n, int lda, double* dtau, double* dS, double* dU, int ldu,
+                 double* dV, int ldv, int* sweeps);
+
+/* 2-norm condition number sigma_max / sigma_min through the values-only path (dA is factored in place); inf when sigma_min == 0, and
+ * whenever R(i,i) == 0 exactly for some i (qr_lstsq's test: an exactly zero column, for one -- R is then exactly singular, and the
+ * iteration would return rounding noise in place of that zero).  Synchronous.  (LAPACK: dgesvd + a division; dtrcon estimates the 1-norm one.) */
+int qr_cond_dev(qr_plan* plan, double* dA, int m, int n, int lda, double* dtau, double* cond);
+
+/* LAPACK dgelss (m >= n): the minimum-norm solution of min ||A X - B|| for any rank -- what section 4's basic solution is not.  Factors
+ * dA, applies Q^T to dB (m x nrhs, ldb >= m), runs the iteration on R^T = Y S Z^T with accumulation and forms X = Y S^+ (Z^T c),
+ * c = (Q^T B)(0:n): S^+ inverts sigma_i > rcond * sigma_0 and zeroes the rest; rcond < 0 selects max(m, n) * DBL_EPSILON as qr_rank_dev
+ * does.  On return rows 0..n-1 of dB hold X, rows n..m-1 are as qr_gels_dev leaves them; dS: the n singular values; *rank (host, may be
+ * NULL) = the number of inverted values.  A zero matrix gives rank 0 and X = 0, not an error.  Host waits as qr_gesvj_dev. */
+int qr_gelss_dev(qr_plan* plan, double* dA, int m, int n, int lda, double* dtau, double* dB, int nrhs, int ldb, double rcond, double* dS,
+                 int* rank);
+
+/* The tall SVD on host pointers, A (m x n, m >= n) untouched: S (n, descending), U (m x n, ld m) and V (n x n, ld n) may each be NULL.
+ * Uses the plan cache of mmqr (qr_release_cached_plans).  Synchronous. */
+int qr_svd(const double* A, int m, int n, double* S, double* U, double* V);
+
+/* LAPACK dgelss on host pointers, A (m x n, m >= n) and B (m x nrhs) untouched: X (n x nrhs, ld n); resid (nrhs doubles, may be NULL) =
+ * ||A x_j - b_j||_2, from the last m - n entries of Q^T b_j and the components along the discarded singular vectors; rank and S (n
+ * doubles) may be NULL.  Uses the plan cache of mmqr.  Synchronous. */
+int qr_lstsq_svd(const double* A, int m, int n, const double* B, int nrhs, double rcond, double* X, double* resid, int* rank, double* S);
 
 #ifdef __cplusplus
 }
