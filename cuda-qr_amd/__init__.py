@@ -42,6 +42,7 @@ QR_PROF_CLASSES = 4
 QR_E_ARG = -101
 QR_E_SINGULAR = -107
 QR_E_NOCONV = -108
+QR_E_NOTPD = -109
 JSVD_BLOCK = 32         # QR_JSVD_BLOCK: the column-block width of the Jacobi schedule
 JSVD_MAX_SWEEPS = 30    # QR_JSVD_MAX_SWEEPS
 PROF_NAMES = ("update_nn", "vta_tn", "panel", "vt_misc")
@@ -141,6 +142,11 @@ _sig("qr_lsacc_solve_dev", C.c_int, _vp, _vp, C.c_int, _vp)
 _sig("qr_lsacc_reset", C.c_int, _vp)
 _sig("qr_lsacc_destroy", C.c_int, _vp)
 _sig("qr_lstsq_chunked", C.c_int, _dp, C.c_longlong, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp)
+_sig("qr_tphqrt_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _ip)
+_sig("qr_tphmqrt_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
+_sig("qr_lsacc_pop_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int)
+_sig("qr_lsacc_slide_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int)
+_sig("qr_lstsq_rolling", C.c_int, _dp, C.c_longlong, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp)
 _sig("qr_jsvd_rounds", C.c_int, C.c_int, _ip, _ip)
 _sig("qr_jsvd_round_pairs", C.c_int, C.c_int, C.c_int, _ip, C.c_int)
 _sig("qr_gesvj_dev", C.c_int, _vp, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _ip)
@@ -443,6 +449,28 @@ def lstsq_chunked(A, B, chunk_rows):
     return (X[:, 0], resid[0]) if vec else (X, resid)
 
 
+def lstsq_rolling(A, B, window, step):
+    """least squares over the windows A[k step : k step + window], k = 0 .. (m - window) // step, through qr_lstsq_rolling: the first
+    window is factored, every later one is one slide (step rows in, step rows out).  Returns (X, resid): X of shape (windows, n, nrhs)
+    -- (windows, n) for a vector B --, resid (windows, nrhs) / (windows,).  Raises QRError: QR_E_SINGULAR for a rank-deficient first
+    window, QR_E_NOTPD when a later window loses full rank."""
+    A = _f(A)
+    m, n = A.shape
+    B = np.asarray(B, dtype=np.float64)
+    vec = B.ndim == 1
+    B = _f(B.reshape(-1, 1) if vec else B)
+    if B.shape[0] != m:
+        raise QRError(f"lstsq_rolling: B has {B.shape[0]} rows, A has {m}", QR_E_ARG)
+    nrhs = B.shape[1]
+    window, step = int(window), int(step)
+    nwin = (m - window) // step + 1 if 1 <= step and n <= window <= m else 1
+    X = np.empty((nwin, nrhs, n))                        # window k: the column-major n x nrhs block
+    resid = np.empty((nwin, nrhs))
+    check(lib.qr_lstsq_rolling(_p(A), m, n, m, _p(B), nrhs, m, window, step, _p(X), _p(resid)), "qr_lstsq_rolling")
+    X = X.transpose(0, 2, 1)
+    return (X[:, :, 0], resid[:, 0]) if vec else (X, resid)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -701,6 +729,22 @@ class Plan:
         check(lib.qr_tpmqrt_dev(self.h, trans.encode(), _dptr(dV), p, n, ldv, _dptr(dT), ldt, _dptr(dC1), ldc1, _dptr(dC2), ldc2, nrhs),
               "qr_tpmqrt_dev")
 
+    def tphqrt(self, dR, n, ldr, dB, p_add, p_del, ldb, dT, ldt):
+        """the signed-row update: dB's first p_add rows are added to the triangle dR, its last p_del rows removed; dB <- V, dT <- the
+        block T.  Waits for the result.  Raises QRError (status QR_E_NOTPD, .info = the failing column + 1) when the removal leaves no
+        positive-definite triangle."""
+        info = C.c_int(0)
+        rc = lib.qr_tphqrt_dev(self.h, _dptr(dR), n, ldr, _dptr(dB), p_add, p_del, ldb, _dptr(dT), ldt, C.byref(info))
+        if rc != 0:
+            e = QRError(f"qr_tphqrt_dev failed: {strerror(rc)} ({rc}), info = {info.value}", rc)
+            e.info = info.value
+            raise e
+
+    def tphmqrt(self, dV, p_add, p_del, n, ldv, dT, ldt, dC1, ldc1, dC2, ldc2, nrhs):
+        """[C1 ; C2] <- the transformation of tphqrt (the one that took [R ; B] to [R' ; 0]) with dV, dT from it"""
+        check(lib.qr_tphmqrt_dev(self.h, _dptr(dV), p_add, p_del, n, ldv, _dptr(dT), ldt, _dptr(dC1), ldc1, _dptr(dC2), ldc2, nrhs),
+              "qr_tphmqrt_dev")
+
     def gesvj(self, jobv, dG, r, n, ldg, dS, dV=None, ldv=0):
         """dgesvj on the device: dG (r x n) <- the left singular vectors, dS <- the values (descending), dV (jobv 'V') <- the right ones;
         returns the sweeps used.  Raises QRError (status QR_E_NOCONV) after JSVD_MAX_SWEEPS sweeps."""
@@ -809,6 +853,15 @@ class LsAccumulator:
     def push(self, dA, p, lda, dB, ldb):
         """fold in p rows [dA | dB]; both buffers are workspace and hold nothing defined afterwards"""
         check(lib.qr_lsacc_push_dev(self.h, _dptr(dA), p, lda, _dptr(dB), ldb), "qr_lsacc_push_dev")
+
+    def pop(self, dA, p, lda, dB, ldb):
+        """remove p rows [dA | dB] that were pushed earlier (inputs untouched); QRError with status QR_E_NOTPD leaves the state as it was"""
+        check(lib.qr_lsacc_pop_dev(self.h, _dptr(dA), p, lda, _dptr(dB), ldb), "qr_lsacc_pop_dev")
+
+    def slide(self, dAnew, pnew, ldan, dBnew, ldbn, dAold, pold, ldao, dBold, ldbo):
+        """add pnew rows and remove pold rows in one pass (inputs untouched); all-or-nothing as pop"""
+        check(lib.qr_lsacc_slide_dev(self.h, _dptr(dAnew), pnew, ldan, _dptr(dBnew), ldbn, _dptr(dAold), pold, ldao, _dptr(dBold), ldbo),
+              "qr_lsacc_slide_dev")
 
     def rows(self):
         r = C.c_longlong()

@@ -205,6 +205,18 @@ int qrd_tp_apply(void* stream, int trans_t, const double* Vk, int ldv, int p, in
 int qrd_tp_colssq_add(void* stream, const double* X, int ldx, int rows, int cols, double* acc);
 int qrd_tp_sqrt(void* stream, const double* in, double* out, int n);
 
+/* signed-row update (qr_downdate.hip, called from qr_downdate.c only -- as above, the stub device layer does not have them): the rows
+ * [0, p_add) of a block count +1, the rows [p_add, p) count -1 (S = diag of those signs).  status: one device int, 0 while all is well;
+ * every launch reads it first and returns at once when it is not 0.
+ * qrd_th_panel: qrd_tp_panel with every inner product over the p rows weighted by S; a column whose d = R(j,j)^2 + b^T S b is <= 0 or
+ * not finite writes col0 + j + 1 to *status and ends the launch (nothing is written back).
+ * qrd_th_apply: W = Tk^T (C1k + Vk^T S C2), C1k -= W, C2 -= Vk W, the layout of qrd_tp_apply.
+ * qrd_th_colssq: acc[c] = max(0, acc[c] + |X(0:p_add, c)|^2 - |X(p_add:p, c)|^2), fixed order.  -7: shape not taken */
+int qrd_th_panel(void* stream, double* Rkk, int ldr, double* Bk, int ldb, int p, int p_add, int w, double* Tk, int ldt, int col0, int* status);
+int qrd_th_apply(void* stream, const double* Vk, int ldv, int p, int p_add, int w, const double* Tk, int ldt, double* C1k, int ldc1,
+                 double* C2, int ldc2, int ncols, const int* status);
+int qrd_th_colssq(void* stream, const double* X, int ldx, int p, int p_add, int cols, double* acc, const int* status);
+
 /* one-sided block Jacobi SVD (qr_svd.hip, called from qr_svd.c only -- as above, the stub device layer does not have them).
  * qrd_jsvd_round: one round of the tournament, one workgroup per block pair: pairs = 2 npairs device ints (p, q) in units of
  * QRD_JSVD_BLOCK columns (p == q: the self-pair of a one-block matrix); G is r x n (ldg), V (n x n, ldv) receives the same rotations

@@ -253,6 +253,7 @@ const char* qr_strerror(int status)
     case QR_E_REFUSED: return "latch mode: the guard refused a full-width tall panel (ill-conditioned or rank-deficient): the factorisation is invalid";
     case QR_E_SINGULAR: return "R has an exactly zero diagonal entry: the matrix is rank deficient, no least-squares solution was computed";
     case QR_E_NOCONV: return "the Jacobi iteration did not reach its threshold in QR_JSVD_MAX_SWEEPS sweeps: the results are not to be used";
+    case QR_E_NOTPD: return "the row removal leaves no positive-definite triangle (rows that were never added, or too few rows left)";
     case QRD_E_NORCCL: return "librccl.so could not be loaded (multi-GPU entry points need RCCL)";
     default:
         if (status > 0) return qrd_error_string(status);
@@ -526,6 +527,7 @@ int qr_plan_destroy(qr_plan* p)
     qrd_host_word_free(p->cq_hword);
     qrd_free(p->pv_d); qrd_free(p->pv_i); qrd_free(p->pv_scatter);
     qrd_free(p->sv_d); qrd_free(p->sv_i); qrd_free(p->sv_t); free(p->sv_h);
+    qrd_free(p->hd_status);
     if (p->s_main) qrd_stream_destroy(p->s_main);
     free(p);
     return 0;

@@ -93,6 +93,19 @@ struct qr_plan {
     int* sv_h;                  /* host image of sv_i (the copies are asynchronous: it has to outlive the call) */
     double* sv_t;               /* 2 x (n x nrhs): Z^T c and its scaled copy (qr_gelss_dev) */
     size_t sv_t_cap;
+    /* signed-row update (qr_downdate.c): allocated on the first call of header section 6b, freed with the plan */
+    int* hd_status;             /* device word: 0, or the column + 1 at which a removal left no positive-definite triangle */
+};
+
+/* the least-squares accumulator (qr_update.c; qr_downdate.c removes rows from it).  One device allocation: R (n x n), Rc (n x n: a
+ * chunk's triangle with explicit zeros below it), Z (n x nrhs), T (32 x n), tau (n), ssq (nrhs).  dd_buf: the workspace of pop / slide,
+ * allocated on their first call: copies of R, Z and ssq, and a block of at most QRD_TP_MAXROWS stacked rows with its right-hand sides */
+struct qr_lsacc {
+    qr_plan* p;
+    int n, nrhs;
+    long long rows;
+    double *buf, *R, *Rc, *Z, *T, *tau, *ssq;
+    double* dd_buf;
 };
 
 /* a cached plan of the host-pointer entry points and its device buffers (qr_host.c) */

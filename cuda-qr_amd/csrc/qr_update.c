@@ -63,13 +63,7 @@ int qr_tpmqrt_dev(qr_plan* p, char trans, const double* dV, int rows, int n, int
     return tpmqrt_core(p->stream, tr, dV, rows, n, ldv, dT, ldt, dC1, ldc1, dC2, ldc2, nrhs);
 }
 
-/* one device allocation: R (n x n), Rc (n x n: a chunk's triangle with explicit zeros below it), Z (n x nrhs), T (32 x n), tau (n), ssq (nrhs) */
-struct qr_lsacc {
-    qr_plan* p;
-    int n, nrhs;
-    long long rows;
-    double *buf, *R, *Rc, *Z, *T, *tau, *ssq;
-};
+/* struct qr_lsacc: qr_plan_internal.h (qr_downdate.c works on it as well) */
 
 int qr_lsacc_reset(qr_lsacc* a)
 {
@@ -103,8 +97,9 @@ int qr_lsacc_destroy(qr_lsacc* a)
 {
     if (!a) return QR_E_ARG;
     int rc = qrd_stream_sync(a->p->stream);      /* launches that read the buffers may still be queued */
-    const int rf = qrd_free(a->buf);
+    const int rf = qrd_free(a->buf), rd = qrd_free(a->dd_buf);
     if (!rc) rc = rf;
+    if (!rc) rc = rd;
     free(a);
     return rc;
 }

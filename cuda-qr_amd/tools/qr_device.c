@@ -24,6 +24,11 @@
  * `./qr_device m n --svd` does nothing else either: the SVD of the matrix (qr_gesvd_dev with U and V, matrix resident in HBM): time,
  * sigma_max, sigma_min, the Jacobi sweeps, ||A - U S V^T||_F / ||A||_F and the two orthogonality errors ||U^T U - I||_F, ||V^T V - I||_F
  * (products formed on the host).
+ *
+ * `./qr_device m n --slide window step` does nothing else either: least squares over the windows [k step, k step + window) of the rows.
+ * The first window is pushed into an accumulator, every later one is one qr_lsacc_slide_dev (step rows in, step rows out, rows resident
+ * in HBM), beside one qr_gels_dev per window (window resident in HBM): both wall times, the time of the host-pointer qr_lstsq_rolling,
+ * the largest solution error against the per-window solve, and the Gram drift ||R_acc^T R_acc - R^T R||_F / ||R^T R||_F at the last window.
  */
 #include <math.h>
 #include <stdio.h>
@@ -231,6 +236,100 @@ static int append_main(int m, int n, int chunk)
     return 0;
 }
 
+/* m x n, one right-hand side, windows of `window` rows every `step` rows: an accumulator that slides against one qr_gels_dev per window */
+static int slide_main(int m, int n, int window, int step)
+{
+    if (n < 1 || window < n || window > m || step < 1 || step > window) { fprintf(stderr, "--slide needs m >= window >= n >= 1 and 1 <= step <= window\n"); return 1; }
+    const int nwin = (m - window) / step + 1;
+    printf("Exact problem size: %dx%d, %d windows of %d rows, %d rows apart\n", m, n, nwin, window, step);
+    const size_t cnt = (size_t) m * n, wc = (size_t) window * n, sc = (size_t) step * n, nn = (size_t) n * n;
+    double *A = malloc(sizeof(double) * cnt), *b = malloc(sizeof(double) * m), *Aw = malloc(sizeof(double) * wc), *F = malloc(sizeof(double) * wc);
+    double *xs = malloc(sizeof(double) * (size_t) nwin * n), *xg = malloc(sizeof(double) * (size_t) nwin * n), *xr = malloc(sizeof(double) * (size_t) nwin * n);
+    double *Ra = malloc(sizeof(double) * nn), *G0 = malloc(sizeof(double) * nn), *G1 = malloc(sizeof(double) * nn);
+    if (!A || !b || !Aw || !F || !xs || !xg || !xr || !Ra || !G0 || !G1) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    for (int i = 0; i < m; i++) b[i] = (double) rand() / RAND_MAX - 0.5;
+    qr_plan* p = NULL;
+    qr_lsacc* acc = NULL;
+    double *dA = NULL, *dtau = NULL, *dB = NULL, *dN = NULL, *dO = NULL, *dbN = NULL, *dbO = NULL, *dX = NULL;
+    if (qr_plan_create(&p, window, n, 0, 0) || qr_lsacc_create(&acc, p, n, 1) || qr_device_malloc((void**) &dA, sizeof(double) * wc) ||
+        qr_device_malloc((void**) &dtau, sizeof(double) * n) || qr_device_malloc((void**) &dB, sizeof(double) * window) ||
+        qr_device_malloc((void**) &dN, sizeof(double) * sc) || qr_device_malloc((void**) &dO, sizeof(double) * sc) ||
+        qr_device_malloc((void**) &dbN, sizeof(double) * step) || qr_device_malloc((void**) &dbO, sizeof(double) * step) ||
+        qr_device_malloc((void**) &dX, sizeof(double) * n)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double elg = 0.0, els = 0.0, elr = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        /* one qr_gels_dev per window; the uploads are not timed: the rows count as resident on both sides */
+        for (int k = 0; k < nwin; k++) {
+            for (int j = 0; j < n; j++) memcpy(Aw + (size_t) j * window, A + (size_t) j * m + (size_t) k * step, sizeof(double) * window);
+            if (qr_copy_to_device(dA, Aw, sizeof(double) * wc) || qr_copy_to_device(dB, b + (size_t) k * step, sizeof(double) * window)) { fprintf(stderr, "copy failed\n"); return 1; }
+            const double t0 = now();
+            if (qr_gels_dev(p, dA, window, n, window, dtau, dB, 1, window) || qr_plan_sync(p)) { fprintf(stderr, "qr_gels_dev failed\n"); return 1; }
+            if (t >= 0) elg += now() - t0;
+            if (qr_copy_to_host(xg + (size_t) k * n, dB, sizeof(double) * n)) { fprintf(stderr, "copy failed\n"); return 1; }
+        }
+        if (qr_copy_to_host(F, dA, sizeof(double) * wc)) { fprintf(stderr, "copy failed\n"); return 1; }       /* the last window's factor */
+        /* the accumulator: window 0 pushed (dA, dB are its workspace), then one slide per window */
+        for (int j = 0; j < n; j++) memcpy(Aw + (size_t) j * window, A + (size_t) j * m, sizeof(double) * window);
+        if (qr_lsacc_reset(acc) || qr_copy_to_device(dA, Aw, sizeof(double) * wc) || qr_copy_to_device(dB, b, sizeof(double) * window)) { fprintf(stderr, "copy failed\n"); return 1; }
+        for (int k = 0; k < nwin; k++) {
+            int rc = 0;
+            if (k > 0) {
+                const size_t o = (size_t) (k - 1) * step, e = o + window;
+                for (int j = 0; j < n; j++) {
+                    memcpy(Aw + (size_t) j * step, A + (size_t) j * m + e, sizeof(double) * step);
+                    memcpy(Aw + sc + (size_t) j * step, A + (size_t) j * m + o, sizeof(double) * step);
+                }
+                if (qr_copy_to_device(dN, Aw, sizeof(double) * sc) || qr_copy_to_device(dO, Aw + sc, sizeof(double) * sc) ||
+                    qr_copy_to_device(dbN, b + e, sizeof(double) * step) || qr_copy_to_device(dbO, b + o, sizeof(double) * step)) { fprintf(stderr, "copy failed\n"); return 1; }
+            }
+            const double t1 = now();
+            rc = k ? qr_lsacc_slide_dev(acc, dN, step, step, dbN, step, dO, step, step, dbO, step) : qr_lsacc_push_dev(acc, dA, window, window, dB, window);
+            if (!rc) rc = qr_lsacc_solve_dev(acc, dX, n, NULL);
+            if (!rc) rc = qr_plan_sync(p);
+            if (rc) { fprintf(stderr, "window %d failed: %s\n", k, qr_strerror(rc)); return 1; }
+            if (t >= 0) els += now() - t1;
+            if (qr_copy_to_host(xs + (size_t) k * n, dX, sizeof(double) * n)) { fprintf(stderr, "copy failed\n"); return 1; }
+        }
+        const double t2 = now();
+        const int rr = qr_lstsq_rolling(A, m, n, m, b, 1, m, window, step, xr, NULL);
+        if (rr) { fprintf(stderr, "qr_lstsq_rolling failed: %s\n", qr_strerror(rr)); return 1; }
+        if (t >= 0) elr += now() - t2;
+    }
+    const double* dR = NULL;
+    int ldr = 0;
+    if (qr_lsacc_factor_dev(acc, &dR, &ldr, NULL, NULL) || qr_copy_to_host(Ra, dR, sizeof(double) * nn)) { fprintf(stderr, "copy failed\n"); return 1; }
+    gram_of_triangle(F, window, n, G0);
+    gram_of_triangle(Ra, ldr, n, G1);
+    double gn = 0.0, gd = 0.0, worst = 0.0, worst_r = 0.0;
+    for (size_t i = 0; i < nn; i++) { gn += (G1[i] - G0[i]) * (G1[i] - G0[i]); gd += G0[i] * G0[i]; }
+    for (int k = 0; k < nwin; k++) {
+        double xn = 0.0, xd = 0.0, rn = 0.0;
+        for (int i = 0; i < n; i++) {
+            const double g = xg[(size_t) k * n + i], ds = xs[(size_t) k * n + i] - g, dr = xr[(size_t) k * n + i] - g;
+            xn += ds * ds; rn += dr * dr; xd += g * g;
+        }
+        if (sqrt(xn / xd) > worst) worst = sqrt(xn / xd);
+        if (sqrt(rn / xd) > worst_r) worst_r = sqrt(rn / xd);
+    }
+    printf(" MMQR ran least squares on %d windows of %dx%d in %f s (avg over %d)   [one qr_gels_dev per window, window resident in HBM]\n",
+           nwin, window, n, elg / TRIALS, TRIALS);
+    printf(" MMQR ran the same by sliding %d rows at a time in %f s (avg over %d)   [accumulator, rows resident in HBM; largest solution error %.2e, Gram drift at the last window %.2e]\n",
+           step, els / TRIALS, TRIALS, worst, sqrt(gn / gd));
+    printf(" MMQR ran the same from host memory in %f s (avg over %d)   [qr_lstsq_rolling, uploads included; largest solution error %.2e]\n",
+           elr / TRIALS, TRIALS, worst_r);
+    qr_lsacc_destroy(acc);
+    qr_device_free(dA); qr_device_free(dtau); qr_device_free(dB); qr_device_free(dN); qr_device_free(dO); qr_device_free(dbN); qr_device_free(dbO); qr_device_free(dX);
+    qr_plan_destroy(p);
+    qr_release_cached_plans();
+    free(A); free(b); free(Aw); free(F); free(xs); free(xg); free(xr); free(Ra); free(G0); free(G1);
+    return 0;
+}
+
 /* ||X^T X - I||_F of the rows x cols column-major X */
 static double orth_err(const double* X, int rows, int cols)
 {
@@ -294,10 +393,15 @@ static int svd_main(int m, int n)
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
+    for (int i = 3; i < argc; i++)
+        if (strcmp(argv[i], "--slide") == 0) {
+            if (i + 2 >= argc) { fprintf(stderr, "--slide needs window and step\n"); return 1; }
+            return slide_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), atoi(argv[i + 2]));
+        }
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--svd") == 0) return svd_main(atoi(argv[1]), atoi(argv[2]));
     for (int i = 3; i < argc; i++) {

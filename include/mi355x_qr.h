@@ -86,6 +86,7 @@ int explicitQR_legacy_status(double* A, double* tau, double* Q, double* R, int m
 #define QR_E_REFUSED  (-106)  /* qr_plan_sync in latch mode (qr_plan_set_guard_mode): a full-width tall panel was refused; result invalid */
 #define QR_E_SINGULAR (-107)  /* qr_lstsq: R(i,i) == 0 exactly for some i (LAPACK dgels INFO > 0); no solution was computed */
 #define QR_E_NOCONV   (-108)  /* section 7: the Jacobi iteration did not reach its threshold in QR_JSVD_MAX_SWEEPS sweeps; results are not to be used */
+#define QR_E_NOTPD    (-109)  /* section 6b: the row removal leaves no positive-definite triangle (rows that were never added, or too few left) */
 const char* qr_strerror(int status);
 
 /* Block sizes used by the drop-in entry points (outer compact-WY block nb: multiple of ib, <= 512, above 256 a multiple of 256;
@@ -472,6 +473,62 @@ int qr_lsacc_destroy(qr_lsacc* acc);
  * (X holds no solution then); QR_E_ARG for chunk_rows < 1. */
 int qr_lstsq_chunked(const double* A, long long m, int n, int lda, const double* B, int nrhs, int ldb,
                      int chunk_rows, double* X, double* resid);
+
+/* ---------------------------------------------------------------------------------------------
+ * 6b. Row removal: the signed-row update of R and sliding-window least squares.  Section 6 can only add rows; here the last p_del rows
+ * of a block are REMOVED while its first p_add rows are added, in one pass: with S = diag(+1 .. +1, -1 .. -1) over the block's rows,
+ * R' is the upper triangle with R'^T R' = R^T R + B^T S B.  The transformation is a product of hyperbolic Householder reflectors
+ * Theta_j = I - tau_j u_j u_j^T Phi, u_j = [e_j ; v_j], Phi = diag(I_n, S), tau_j (1 + v_j^T S v_j) = 2, which keep the signed Gram
+ * matrix [R ; B]^T Phi [R ; B]; per column dlarfg's formulas hold with every inner product over the block's rows weighted by S:
+ * d = R(j,j)^2 + b^T S b, beta = -sign(R(j,j)) sqrt(d), v = b / (R(j,j) - beta), tau = (beta - R(j,j)) / beta.  d is formed without
+ * cancellation as (h - |b_del|)(h + |b_del|), h = hypot(R(j,j), |b_add|).  A panel of QR_TPQRT_PANEL columns is I - U T U^T Phi with
+ * the compact-WY recursion of section 6 on V^T S V.  No reference counterpart; no LAPACK one either (LINPACK dchdd removes one row with
+ * plane rotations).  Conventions of section 6: status return, bad arguments return QR_E_ARG before anything touches a device, fixed-order
+ * sums, bitwise-equal repeats, fp64, column-major; the same row limit, now on p_add + p_del.
+ * Failure: a column with d <= 0, or d not finite, means that the rows to be removed are not contained in the matrix R belongs to (or
+ * that too few rows would be left): there is no positive-definite R'.  The kernel that meets it writes the column + 1 into a device
+ * word that hangs off the plan and stops; every later launch of the same call reads the word first and returns at once; the host reads
+ * it once, at the end of the call: QR_E_NOTPD.
+ * Stability: the method is NOT backward stable in the sense the orthogonal update is.  Its error grows with ||R R'^{-1}||, the
+ * conditioning of the removal itself: removing rows that carry most of a column's mass loses that many digits, as it must -- the
+ * triangle no longer holds the information.  A removal that leaves a well-conditioned R' from a well-conditioned R is as accurate as
+ * the update (the Gram identity to n eps in the tests).  Adding and removing in one pass keeps d further from zero than removing first.
+ * ------------------------------------------------------------------------------------------- */
+
+/* qr_tpqrt_dev with signed rows: dB is (p_add + p_del) x n, its first p_add rows are added, its last p_del rows removed; p_add >= 0,
+ * p_del >= 0, 1 <= p_add + p_del <= qr_tpqrt_max_rows(), ldb >= p_add + p_del.  dR, dB (<- V), dT as qr_tpqrt_dev.  An exactly zero
+ * column of B: tau = 0, nothing touched.  The host thread waits once, at the end, and reads the status word: QR_E_NOTPD with *info
+ * (host, may be NULL) = the failing column + 1 -- dR and dB are undefined then -- else 0 and *info = 0.  With p_del == 0 this IS
+ * qr_tpqrt_dev (the same launches, bitwise the same result) followed by the wait.  Two launches per QR_TPQRT_PANEL columns. */
+int qr_tphqrt_dev(qr_plan* plan, double* dR, int n, int ldr, double* dB, int p_add, int p_del, int ldb, double* dT, int ldt, int* info);
+
+/* Applies to [C1 ; C2] (dC1: n x nrhs, ldc1 >= n; dC2: (p_add + p_del) x nrhs) the transformation that took [R ; B] to [R' ; 0], with
+ * dV, dT from qr_tphqrt_dev: panel by panel W = T^T (C1 + V^T S C2), C1 -= W, C2 -= V W.  That one direction is what right-hand sides
+ * need; it keeps |C1(:, c)|^2 + C2(:, c)^T S C2(:, c).  Stream-ordered, no host wait.  One launch per panel. */
+int qr_tphmqrt_dev(qr_plan* plan, const double* dV, int p_add, int p_del, int n, int ldv, const double* dT, int ldt,
+                   double* dC1, int ldc1, double* dC2, int ldc2, int nrhs);
+
+/* The accumulator of section 6 with rows leaving:
+ *   qr_lsacc_pop_dev    removes p >= 1 rows [dA | dB] that were pushed earlier (dA: p x n, lda >= p; dB: p x nrhs, ldb >= p; both
+ *                       untouched), in blocks of at most qr_tpqrt_max_rows().  Z rides along; the sums of squares become rss - |E|^2, E =
+ *                       what the transformation leaves in the removed rows of the right-hand sides, clamped at 0.
+ *   qr_lsacc_slide_dev  adds pnew rows and removes pold rows in one pass: new stacked over old in the accumulator's workspace, in blocks
+ *                       with p_add + p_del <= qr_tpqrt_max_rows().  The inputs are untouched.
+ * Both are all-or-nothing: they work on copies of R, Z and the sums and commit them with device copies after the last block succeeded;
+ * on QR_E_NOTPD the accumulator is bitwise what it was.  They wait once for the status word.  More rows removed than held: QR_E_ARG.
+ * Fewer than n rows left -- removing every row included --: QR_E_NOTPD before any launch (no triangle of full rank can remain; to
+ * start over use qr_lsacc_reset).  The workspace (a copy of R, Z and the sums, one block of qr_tpqrt_max_rows() rows) is allocated on the first call and freed by qr_lsacc_destroy. */
+int qr_lsacc_pop_dev(qr_lsacc* acc, const double* dA, int p, int lda, const double* dB, int ldb);
+int qr_lsacc_slide_dev(qr_lsacc* acc, const double* dAnew, int pnew, int ldan, const double* dBnew, int ldbn,
+                       const double* dAold, int pold, int ldao, const double* dBold, int ldbo);
+
+/* Least squares over a window that moves, on host pointers; A (m x n, lda >= m) and B (m x nrhs, ldb >= m) are untouched.  Window k is
+ * rows [k step, k step + window), k = 0 .. (m - window) / step.  X: one n x nrhs solution (ld n) per window, one after the other;
+ * resid: nrhs values per window, may be NULL.  The first window is pushed, each later one is ONE slide (step rows in, step rows out).
+ * QR_E_ARG for window < n, step < 1, step > window, window > m; QR_E_SINGULAR as qr_lstsq_chunked (first window); QR_E_NOTPD when a
+ * later window loses full rank.  Uses the plan cache of mmqr, keyed on (window, n).  Synchronous. */
+int qr_lstsq_rolling(const double* A, long long m, int n, int lda, const double* B, int nrhs, int ldb, int window, int step,
+                     double* X, double* resid);
 
 /* ---------------------------------------------------------------------------------------------
  * 7. Singular values, SVD and minimum-norm least squares of rank-deficient systems.  With A = Q R (m x n, m >= n) and the SVD of the
