@@ -155,6 +155,14 @@ _sig("qr_cond_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _dp)
 _sig("qr_gelss_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _ip)
 _sig("qr_svd", C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp)
 _sig("qr_lstsq_svd", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip, _dp)
+_ll = C.c_longlong
+_sig("qr_batched_max_rows", C.c_int, C.c_int)
+_sig("qr_geqrf_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, C.c_int)
+_sig("qr_ormqr_batched_dev", C.c_int, _vp, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, C.c_int)
+_sig("qr_orgqr_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, _ll, C.c_int)
+_sig("qr_gels_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int)
+_sig("qr_thin_batched", C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp)
+_sig("qr_lstsq_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -471,6 +479,48 @@ def lstsq_rolling(A, B, window, step):
     return (X[:, :, 0], resid[:, 0]) if vec else (X, resid)
 
 
+def batched_max_rows(ncols):
+    """the most rows the batched calls take for ncols columns held in LDS (qr_batched_max_rows; 0: too many columns; no device)"""
+    return lib.qr_batched_max_rows(int(ncols))
+
+
+def _packed_batch(A, what):
+    """(batch, rows, cols) -> the packed column-major batch (a C-contiguous (batch, cols, rows) array)"""
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 3:
+        raise QRError(f"{what}: expected an array of shape (batch, rows, cols), got {A.shape}", QR_E_ARG)
+    return np.ascontiguousarray(A.transpose(0, 2, 1))
+
+
+def qr_batched(A):
+    """the thin QR of every matrix of A (batch, m, n), m >= n, through qr_thin_batched: returns Q (batch, m, n) and R (batch, n, n)"""
+    At = _packed_batch(A, "qr_batched")
+    batch, n, m = At.shape
+    Q = np.empty((batch, n, m))
+    R = np.empty((batch, n, n))
+    check(lib.qr_thin_batched(_p(At), m, n, batch, _p(Q), _p(R)), "qr_thin_batched")
+    return Q.transpose(0, 2, 1), R.transpose(0, 2, 1)
+
+
+def lstsq_batched(A, B):
+    """min ||A_q X_q - B_q|| for every matrix of A (batch, m, n) and B (batch, m, nrhs) through qr_lstsq_batched: returns (X, resid,
+    info) with X (batch, n, nrhs), resid[q, j] = ||A_q x_j - b_j|| and info[q] = 0, or i + 1 for the smallest i with R_q(i,i) == 0
+    exactly (X[q] then holds no solution; the other matrices are solved).  A singular matrix does not raise."""
+    At = _packed_batch(A, "lstsq_batched")
+    Bt = _packed_batch(B, "lstsq_batched")
+    batch, n, m = At.shape
+    if Bt.shape[0] != batch or Bt.shape[2] != m:
+        raise QRError(f"lstsq_batched: B is {Bt.shape[0]} matrices of {Bt.shape[2]} rows, A is {batch} of {m}", QR_E_ARG)
+    nrhs = Bt.shape[1]
+    X = np.empty((batch, nrhs, n))
+    resid = np.empty((batch, nrhs))
+    info = np.zeros(max(batch, 1), dtype=np.intc)
+    rc = lib.qr_lstsq_batched(_p(At), m, n, _p(Bt), nrhs, batch, _p(X), _p(resid), info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_batched")
+    return X.transpose(0, 2, 1), resid, info[:batch].astype(np.int64)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -744,6 +794,25 @@ class Plan:
         """[C1 ; C2] <- the transformation of tphqrt (the one that took [R ; B] to [R' ; 0]) with dV, dT from it"""
         check(lib.qr_tphmqrt_dev(self.h, _dptr(dV), p_add, p_del, n, ldv, _dptr(dT), ldt, _dptr(dC1), ldc1, _dptr(dC2), ldc2, nrhs),
               "qr_tphmqrt_dev")
+
+    def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
+        """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""
+        check(lib.qr_geqrf_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, batch), "qr_geqrf_batched_dev")
+
+    def ormqr_batched(self, trans, dA, m, n, lda, strideA, dtau, stridetau, dC, nrhs, ldc, strideC, batch):
+        """dC_q <- Q_q^T dC_q (trans 'T') or Q_q dC_q ('N') with the factors of geqrf_batched"""
+        check(lib.qr_ormqr_batched_dev(self.h, trans.encode(), _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, _dptr(dC), nrhs, ldc,
+                                       strideC, batch), "qr_ormqr_batched_dev")
+
+    def orgqr_batched(self, dA, m, n, lda, strideA, dtau, stridetau, dQ, ldq, strideQ, batch):
+        """the thin m x n Q of every matrix into dQ"""
+        check(lib.qr_orgqr_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, _dptr(dQ), ldq, strideQ, batch),
+              "qr_orgqr_batched_dev")
+
+    def gels_batched(self, dA, m, n, lda, strideA, dtau, stridetau, dB, nrhs, ldb, strideB, dinfo, batch):
+        """dgels per matrix: dA factored in place, rows 0..n-1 of dB_q <- X_q; dinfo (batch device ints): 0 or the first zero pivot + 1"""
+        check(lib.qr_gels_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, _dptr(dB), nrhs, ldb, strideB,
+                                      _dptr(dinfo), batch), "qr_gels_batched_dev")
 
     def gesvj(self, jobv, dG, r, n, ldg, dS, dV=None, ldv=0):
         """dgesvj on the device: dG (r x n) <- the left singular vectors, dS <- the values (descending), dV (jobv 'V') <- the right ones;

@@ -1,0 +1,147 @@
+/* qr_batched.c -- factorisation and least squares of many small matrices at once (mi355x_qr.h section 8).
+ *
+ *   qr_geqrf_batched_dev   one launch: a wave or a workgroup per matrix (qrd_b_geqrf; the route follows from (m, n) alone)
+ *   qr_ormqr_batched_dev   one launch (qrd_b_ormqr);  qr_orgqr_batched_dev: the identity written on the device, then ormqr 'N'
+ *   qr_gels_batched_dev    one fused launch while n + nrhs columns fit the kernel (the right-hand sides ride along as columns that are
+ *                          updated but never factored, the back substitution runs in the same kernel); else geqrf, ormqr 'T', qrd_b_trsm
+ *   qr_thin_batched, qr_lstsq_batched   the same on host pointers, packed batches
+ *
+ * The plan supplies the stream; its shape does not bound m and n.  Nothing here waits on the host except the host-pointer twins.
+ *
+ * Kept out of qr_host.c for the reason qr_solve.c is: the sanitizer and stub builds compile qr_host.c against a stub device layer that
+ * has none of the launch wrappers called here. */
+#define _POSIX_C_SOURCE 200809L
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../include/mi355x_qr.h"
+#include "qr_device.h"
+#include "qr_plan_internal.h"
+
+#define CHECK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+int qr_batched_max_rows(int ncols) { return qrd_b_max_rows(ncols); }
+
+/* the shape of one matrix of the batch and its place in it */
+static int bad_shape(int m, int n, int lda, long long strideA, long long stridetau, int batch)
+{
+    return n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || lda < m || strideA < (long long) lda * n || stridetau < n ||
+           batch < 0;
+}
+
+/* a block of `cols` columns beside it: at least m rows apart, matrices at least ld * cols apart */
+static int bad_block(int m, int cols, int ld, long long stride) { return cols < 1 || ld < m || stride < (long long) ld * cols; }
+
+int qr_geqrf_batched_dev(qr_plan* p, double* dA, int m, int n, int lda, long long strideA, double* dtau, long long stridetau, int batch)
+{
+    if (!p || !dA || !dtau || bad_shape(m, n, lda, strideA, stridetau, batch)) return QR_E_ARG;
+    if (batch == 0) return 0;
+    return qrd_b_geqrf(p->stream, dA, m, n, lda, (size_t) strideA, dtau, (size_t) stridetau, NULL, 0, 0, 0, NULL, batch);
+}
+
+int qr_ormqr_batched_dev(qr_plan* p, char trans, const double* dA, int m, int n, int lda, long long strideA, const double* dtau,
+                         long long stridetau, double* dC, int nrhs, int ldc, long long strideC, int batch)
+{
+    if (!p || !dA || !dtau || !dC || (trans != 'T' && trans != 'N') || bad_shape(m, n, lda, strideA, stridetau, batch) ||
+        bad_block(m, nrhs, ldc, strideC))
+        return QR_E_ARG;
+    if (batch == 0) return 0;
+    return qrd_b_ormqr(p->stream, trans == 'T', dA, m, n, lda, (size_t) strideA, dtau, (size_t) stridetau, dC, nrhs, ldc, (size_t) strideC, batch);
+}
+
+int qr_orgqr_batched_dev(qr_plan* p, const double* dA, int m, int n, int lda, long long strideA, const double* dtau, long long stridetau,
+                         double* dQ, int ldq, long long strideQ, int batch)
+{
+    if (!p || !dA || !dtau || !dQ || bad_shape(m, n, lda, strideA, stridetau, batch) || bad_block(m, n, ldq, strideQ)) return QR_E_ARG;
+    if (batch == 0) return 0;
+    CHECK(qrd_b_eye(p->stream, dQ, m, n, ldq, (size_t) strideQ, batch));
+    return qrd_b_ormqr(p->stream, 0, dA, m, n, lda, (size_t) strideA, dtau, (size_t) stridetau, dQ, n, ldq, (size_t) strideQ, batch);
+}
+
+int qr_gels_batched_dev(qr_plan* p, double* dA, int m, int n, int lda, long long strideA, double* dtau, long long stridetau, double* dB,
+                        int nrhs, int ldb, long long strideB, int* dinfo, int batch)
+{
+    if (!p || !dA || !dtau || !dB || !dinfo || bad_shape(m, n, lda, strideA, stridetau, batch) || bad_block(m, nrhs, ldb, strideB))
+        return QR_E_ARG;
+    if (batch == 0) return 0;
+    const size_t sa = (size_t) strideA, st = (size_t) stridetau, sb = (size_t) strideB;
+    if (nrhs <= QR_BATCHED_MAX_N - n && m <= qrd_b_max_rows(n + nrhs))      /* fused: [A | B] in one kernel */
+        return qrd_b_geqrf(p->stream, dA, m, n, lda, sa, dtau, st, dB, nrhs, ldb, sb, dinfo, batch);
+    CHECK(qrd_b_geqrf(p->stream, dA, m, n, lda, sa, dtau, st, NULL, 0, 0, 0, NULL, batch));
+    CHECK(qrd_b_ormqr(p->stream, 1, dA, m, n, lda, sa, dtau, st, dB, nrhs, ldb, sb, batch));
+    return qrd_b_trsm(p->stream, dA, n, lda, sa, dB, nrhs, ldb, sb, dinfo, batch);
+}
+
+/* the host-pointer twins: a plan of their own, one device allocation, packed batches */
+int qr_thin_batched(const double* A, int m, int n, int batch, double* Q, double* R)
+{
+    if (!A || !Q || !R || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || batch < 0) return QR_E_ARG;
+    if (batch == 0) return 0;
+    const size_t mn = (size_t) m * n, nb = (size_t) batch;
+    qr_plan* p = NULL;
+    CHECK(qr_plan_create(&p, m, n, 0, 0));
+    double* d = NULL;
+    double *dA = NULL, *dQ = NULL, *dtau = NULL;
+    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (2 * mn + (size_t) n));
+    if (!rc) { dA = d; dQ = d + nb * mn; dtau = dQ + nb * mn; }
+    double* F = (double*) malloc(sizeof(double) * nb * mn);
+    if (!rc && !F) rc = QR_E_ALLOC;
+    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
+    if (!rc) rc = qr_geqrf_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, batch);
+    if (!rc) rc = qr_orgqr_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dQ, m, (long long) mn, batch);
+    if (!rc) rc = qrd_d2h(p->stream, Q, dQ, sizeof(double) * nb * mn);
+    if (!rc) rc = qrd_d2h(p->stream, F, dA, sizeof(double) * nb * mn);
+    const int rs = qrd_stream_sync(p->stream);
+    if (!rc) rc = rs;
+    if (!rc)
+        for (size_t q = 0; q < nb; ++q)
+            for (int c = 0; c < n; ++c)
+                for (int r = 0; r < n; ++r) R[q * n * n + (size_t) c * n + r] = r <= c ? F[q * mn + (size_t) c * m + r] : 0.0;
+    free(F);
+    if (d) qrd_free(d);
+    qr_plan_destroy(p);
+    return rc;
+}
+
+int qr_lstsq_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, double* X, double* resid, int* info)
+{
+    if (!A || !B || !X || !info || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || nrhs < 1 || batch < 0) return QR_E_ARG;
+    if (batch == 0) return 0;
+    const size_t mn = (size_t) m * n, mr = (size_t) m * nrhs, nb = (size_t) batch;
+    qr_plan* p = NULL;
+    CHECK(qr_plan_create(&p, m, n, 0, 0));
+    double* d = NULL;
+    int* dinfo = NULL;
+    double *dA = NULL, *dB = NULL, *dtau = NULL;
+    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (mn + mr + (size_t) n));
+    if (!rc) { dA = d; dB = d + nb * mn; dtau = dB + nb * mr; }
+    if (!rc) rc = qrd_malloc((void**) &dinfo, sizeof(int) * nb);
+    double* C = (double*) malloc(sizeof(double) * nb * mr);
+    if (!rc && !C) rc = QR_E_ALLOC;
+    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
+    if (!rc) rc = qrd_h2d(p->stream, dB, B, sizeof(double) * nb * mr);
+    if (!rc) rc = qr_gels_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dB, nrhs, m, (long long) mr, dinfo, batch);
+    if (!rc) rc = qrd_d2h(p->stream, C, dB, sizeof(double) * nb * mr);
+    if (!rc) rc = qrd_d2h(p->stream, info, dinfo, sizeof(int) * nb);
+    const int rs = qrd_stream_sync(p->stream);
+    if (!rc) rc = rs;
+    if (!rc)
+        for (size_t q = 0; q < nb; ++q) {
+            for (int j = 0; j < nrhs; ++j) {
+                const double* c = C + q * mr + (size_t) j * m;
+                memcpy(X + (q * nrhs + j) * n, c, sizeof(double) * (size_t) n);
+                if (resid) {
+                    double s = 0.0;
+                    for (int i = n; i < m; ++i) s += c[i] * c[i];
+                    resid[q * nrhs + j] = sqrt(s);
+                }
+            }
+            if (info[q]) rc = QR_E_SINGULAR;
+        }
+    free(C);
+    if (dinfo) qrd_free(dinfo);
+    if (d) qrd_free(d);
+    qr_plan_destroy(p);
+    return rc;
+}

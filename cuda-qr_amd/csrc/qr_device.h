@@ -261,6 +261,27 @@ int qrd_pivot_column(void* stream, const qrd_pivot_ws* w, double* A, int lda, in
 int qrd_pivot_scatter(void* stream, const double* B, int ldb, int n, int nrhs, int r, const int* jpvt, double* S);
 int qrd_pivot_resid(void* stream, const double* B, int ldb, int r0, int m, int nrhs, double* resid);
 
+/* batched small matrices (qr_batched.hip, called from qr_batched.c only -- as above, the stub device layer does not have them).  Matrix
+ * q of a batch is at base + q * stride (doubles), column-major.  The route is chosen from (m, columns held) alone: one wave per matrix
+ * for m <= 64 and <= 32 columns (qrd_b_wave_route), else one workgroup per matrix with the matrix in LDS.
+ * qrd_b_max_rows: the rows that fit for every column count of ncols' class (<= 32: 512, <= 64: 256; 0: too many columns);
+ * qrd_b_fits: whether this very shape fits (m <= QRD_B_MAX_ROWS and ncols columns at a leading dimension of 2 mod 32 within 160 KiB).
+ * qrd_b_geqrf: dgeqr2 of every A; nrhs > 0 (the fused gels): B's columns ride along (B <- Q^T B; n + nrhs columns are held), info[q] = 0
+ * or the smallest i + 1 with R(i,i) == 0, and where it is 0 rows 0..n-1 of B <- R^-1 of them, all in the one launch.
+ * qrd_b_ormqr: C <- Q^T C (trans_t = 1) or Q C (0), one launch.  qrd_b_eye: the m x n identity.  qrd_b_trsm: info and the back
+ * substitution on their own (n <= QRD_B_MAX_N, any nrhs).  batch <= 0: nothing is launched.  -7: shape not taken */
+#define QRD_B_MAX_N 64
+#define QRD_B_MAX_ROWS 512
+int qrd_b_max_rows(int ncols);
+int qrd_b_fits(int m, int ncols);
+int qrd_b_wave_route(int m, int ncols);
+int qrd_b_geqrf(void* stream, double* A, int m, int n, int lda, size_t strideA, double* tau, size_t stridetau, double* B, int nrhs, int ldb,
+                size_t strideB, int* info, int batch);
+int qrd_b_ormqr(void* stream, int trans_t, const double* A, int m, int n, int lda, size_t strideA, const double* tau, size_t stridetau,
+                double* Cm, int nrhs, int ldc, size_t strideC, int batch);
+int qrd_b_eye(void* stream, double* Q, int m, int n, int ldq, size_t strideQ, int batch);
+int qrd_b_trsm(void* stream, const double* A, int n, int lda, size_t strideA, double* B, int nrhs, int ldb, size_t strideB, int* info, int batch);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

@@ -29,6 +29,10 @@
  * The first window is pushed into an accumulator, every later one is one qr_lsacc_slide_dev (step rows in, step rows out, rows resident
  * in HBM), beside one qr_gels_dev per window (window resident in HBM): both wall times, the time of the host-pointer qr_lstsq_rolling,
  * the largest solution error against the per-window solve, and the Gram drift ||R_acc^T R_acc - R^T R||_F / ||R^T R||_F at the last window.
+ *
+ * `./qr_device m n --batched count` does nothing else either: `count` seeded m x n matrices are factored in one qr_geqrf_batched_dev
+ * call (batch resident in HBM), Q formed by qr_orgqr_batched_dev: the time of the factorisation and the worst backward error
+ * ||A - Q R||_F / ||A||_F and orthogonality error ||Q^T Q - I||_F over the batch (products formed on the host).
  */
 #include <math.h>
 #include <stdio.h>
@@ -391,9 +395,71 @@ static int svd_main(int m, int n)
     return 0;
 }
 
+/* count matrices of m x n in one batched call */
+static int batched_main(int m, int n, int count)
+{
+    if (n < 1 || n > QR_BATCHED_MAX_N || m < n || count < 1) {     /* (how tall a matrix may be is the library's answer: QR_E_ARG below) */
+        fprintf(stderr, "--batched needs count >= 1 and 1 <= n <= %d, n <= m\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d matrices of %dx%d\n", count, m, n);
+    const size_t mn = (size_t) m * n, cnt = mn * count;
+    double *A = malloc(sizeof(double) * cnt), *F = malloc(sizeof(double) * cnt), *Q = malloc(sizeof(double) * cnt);
+    if (!A || !F || !Q) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    qr_plan* p = NULL;
+    double *dA = NULL, *dQ = NULL, *dtau = NULL;
+    if (qr_plan_create(&p, m, n, 0, 0) || qr_device_malloc((void**) &dA, sizeof(double) * cnt) || qr_device_malloc((void**) &dQ, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dtau, sizeof(double) * (size_t) n * count)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dA, A, sizeof(double) * cnt)) { fprintf(stderr, "copy failed\n"); return 1; }
+        const double t0 = now();
+        int rc = qr_geqrf_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, count);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc) {
+            fprintf(stderr, "qr_geqrf_batched_dev failed: %s%s\n", qr_strerror(rc), rc == QR_E_ARG ? " (the matrix does not fit the LDS: see qr_batched_max_rows)" : "");
+            return 1;
+        }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_orgqr_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dQ, m, (long long) mn, count) || qr_plan_sync(p) ||
+        qr_copy_to_host(F, dA, sizeof(double) * cnt) || qr_copy_to_host(Q, dQ, sizeof(double) * cnt)) {
+        fprintf(stderr, "qr_orgqr_batched_dev failed\n");
+        return 1;
+    }
+    double worst = 0.0, worst_o = 0.0;
+    for (int q = 0; q < count; q++) {
+        const double *a = A + q * mn, *f = F + q * mn, *qq = Q + q * mn;
+        double num = 0.0, den = 0.0;
+        for (int j = 0; j < n; j++)
+            for (int i = 0; i < m; i++) {
+                double s = -a[(size_t) j * m + i];
+                for (int k = 0; k <= j; k++) s += qq[(size_t) k * m + i] * f[(size_t) j * m + k];
+                num += s * s;
+                den += a[(size_t) j * m + i] * a[(size_t) j * m + i];
+            }
+        if (sqrt(num / den) > worst) worst = sqrt(num / den);
+        const double o = orth_err(qq, m, n);
+        if (o > worst_o) worst_o = o;
+    }
+    const double flops = (2.0 * m * (double) n * n - 2.0 * (double) n * n * n / 3.0) * count;
+    printf(" MMQR ran QR on %d %dx%d matrices in %f s (avg over %d)   [batch resident in HBM, %.1f GFLOP/s fp64]\n", count, m, n, el / TRIALS,
+           TRIALS, flops / (el / TRIALS) / 1e9);
+    printf(" worst ||A - Q R|| / ||A|| = %.2e   worst ||Q^T Q - I|| = %.2e\n", worst, worst_o);
+    qr_device_free(dA); qr_device_free(dQ); qr_device_free(dtau);
+    qr_plan_destroy(p);
+    free(A); free(F); free(Q);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -401,6 +467,11 @@ int main(int argc, char** argv)
         if (strcmp(argv[i], "--slide") == 0) {
             if (i + 2 >= argc) { fprintf(stderr, "--slide needs window and step\n"); return 1; }
             return slide_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), atoi(argv[i + 2]));
+        }
+    for (int i = 3; i < argc; i++)
+        if (strcmp(argv[i], "--batched") == 0) {
+            if (i + 1 >= argc) { fprintf(stderr, "--batched needs a count\n"); return 1; }
+            return batched_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
         }
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--svd") == 0) return svd_main(atoi(argv[1]), atoi(argv[2]));

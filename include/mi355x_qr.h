@@ -606,6 +606,72 @@ int qr_svd(const double* A, int m, int n, double* S, double* U, double* V);
  * doubles) may be NULL.  Uses the plan cache of mmqr.  Synchronous. */
 int qr_lstsq_svd(const double* A, int m, int n, const double* B, int nrhs, double rcond, double* X, double* resid, int* rank, double* S);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8. Batched factorisation and least squares of small matrices: many independent m x n problems (m >= n, n <= QR_BATCHED_MAX_N,
+ * m within what n columns leave of the LDS, see qr_batched_max_rows) in one call -- per-series regressions, per-element fits, what rocSOLVER's geqrf_strided_batched and
+ * torch.linalg.qr on a batch are used for.  Matrix q of a batch lives at base + q * stride; it is column-major and strides count doubles
+ * (a packed batch: lda = m, strideA = m * n, stridetau = n).  No reference counterpart (the reference factors one matrix per call).
+ *
+ * The results follow LAPACK dgeqr2 / dlarfg exactly: beta = -sign(alpha) hypot(alpha, |x|), tau = (beta - alpha) / beta,
+ * v = x / (alpha - beta); x == 0 exactly gives tau = 0 and leaves the column unchanged (so the last column of a square matrix has
+ * tau = 0); R on and above the diagonal, V below it with an implicit unit diagonal.  R, V and tau agree with LAPACK's up to rounding,
+ * signs included.
+ *
+ * One wave factors a matrix of m <= 64 rows and at most 32 columns in registers (four matrices per workgroup); anything larger is
+ * factored by one workgroup with the matrix resident in LDS.  The route follows from the shape alone, never from `batch` or a matrix's
+ * index, and every sum runs in a fixed order: repeated calls are bitwise equal, and a matrix's result is bitwise independent of the
+ * batch count and of its position in the batch.  No atomics.
+ *
+ * The plan supplies the stream only: m and n of a call are not bound by the plan's shape.  Calls queue on the plan's stream and do not
+ * wait on the host; geqrf and ormqr are one launch each, orgqr two, gels one or three (below), whatever `batch` is.  Bad arguments return
+ * QR_E_ARG before anything touches a device: a NULL plan or pointer, m < n, n < 1, n > QR_BATCHED_MAX_N, an m that does not fit (below),
+ * ld* < m, nrhs < 1, an unknown trans, a stride smaller than the block it steps over (strideA < lda * n, stridetau < n, strideC <
+ * ldc * nrhs, ...), batch < 0.  batch == 0 returns 0 and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define QR_BATCHED_MAX_N 64
+
+/* The rows the calls of this section are certain to take for ncols columns held in LDS: 512 for 1 <= ncols <= 32, 256 for
+ * 33 <= ncols <= 64, 0 otherwise (160 KiB of LDS at a leading dimension of m + 2: 32 * 514 and 64 * 258 doubles, plus the small
+ * arrays).  The value is that of the widest matrix of its class; a narrower one is taken while it fits: m <= 512 and n columns at the
+ * leading dimension ld = the smallest value >= m that is 2 mod 32, n * ld + 72 doubles within 160 KiB (300 x 40 is taken, 300 x 64 is
+ * not).  What does not fit is QR_E_ARG.  No device is touched. */
+int qr_batched_max_rows(int ncols);
+
+/* LAPACK dgeqr2 of every matrix in place: R and V over dA, tau (n per matrix) to dtau. */
+int qr_geqrf_batched_dev(qr_plan* plan, double* dA, int m, int n, int lda, long long strideA,
+                         double* dtau, long long stridetau, int batch);
+
+/* LAPACK dormqr, side 'L': dC (m x nrhs per matrix, any nrhs >= 1) <- Q^T dC (trans 'T') or Q dC ('N') from the factors of
+ * qr_geqrf_batched_dev. */
+int qr_ormqr_batched_dev(qr_plan* plan, char trans, const double* dA, int m, int n, int lda, long long strideA,
+                         const double* dtau, long long stridetau,
+                         double* dC, int nrhs, int ldc, long long strideC, int batch);
+
+/* LAPACK dorgqr: the thin m x n Q of every matrix into dQ (the identity written on the device, then ormqr 'N'). */
+int qr_orgqr_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda, long long strideA,
+                         const double* dtau, long long stridetau,
+                         double* dQ, int ldq, long long strideQ, int batch);
+
+/* LAPACK dgels ('N', m >= n) per matrix: dA is factored in place, dB (m x nrhs) receives X in rows 0..n-1; the sum of squares of rows
+ * n..m-1 of a column is that column's residual sum of squares.  dinfo (batch device ints): 0, or i + 1 for the smallest i with
+ * R(i,i) == 0 exactly; such a matrix's dB holds Q^T B and no solve is done for it, the others are unaffected, and the call still returns 0.
+ * One fused launch when n + nrhs <= QR_BATCHED_MAX_N and m <= qr_batched_max_rows(n + nrhs): the right-hand sides ride along as extra
+ * columns that are updated but never factored, and the back substitution runs in the same kernel (the route then follows from
+ * (m, n + nrhs)).  Otherwise the composition geqrf, ormqr 'T', a batched back substitution. */
+int qr_gels_batched_dev(qr_plan* plan, double* dA, int m, int n, int lda, long long strideA,
+                        double* dtau, long long stridetau,
+                        double* dB, int nrhs, int ldb, long long strideB, int* dinfo, int batch);
+
+/* The thin QR of a packed batch on host pointers (A untouched; lda = m, stride = m * n): Q m x n and R n x n (zeros below the diagonal)
+ * per matrix.  Creates a plan of its own.  Synchronous. */
+int qr_thin_batched(const double* A, int m, int n, int batch, double* Q, double* R);
+
+/* dgels on a packed batch on host pointers (A: m x n, B: m x nrhs per matrix, both untouched): X n x nrhs per matrix, resid (nrhs per
+ * matrix, may be NULL) = ||A x_j - b_j||_2, info[batch] as dinfo above.  Returns QR_E_SINGULAR if any info entry is non-zero (X of such a
+ * matrix holds no solution; the others are valid).  Synchronous. */
+int qr_lstsq_batched(const double* A, int m, int n, const double* B, int nrhs, int batch,
+                     double* X, double* resid, int* info);
+
 #ifdef __cplusplus
 }
 #endif
