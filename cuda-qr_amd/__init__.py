@@ -163,6 +163,12 @@ _sig("qr_orgqr_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, 
 _sig("qr_gels_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int)
 _sig("qr_thin_batched", C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp)
 _sig("qr_lstsq_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip)
+_sig("qr_geqp3_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, C.c_int)
+_sig("qr_rank_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, C.c_double, _vp, C.c_int)
+for _name in ("qr_gelsp_batched_dev", "qr_gelsy_batched_dev"):
+    _sig(_name, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, C.c_double, _vp, _vp, C.c_int)
+_sig("qr_thin_pivoted_batched", C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip)
+_sig("qr_lstsq_pivoted_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _ip, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -521,6 +527,38 @@ def lstsq_batched(A, B):
     return X.transpose(0, 2, 1), resid, info[:batch].astype(np.int64)
 
 
+def qr_pivoted_batched(A):
+    """the column-pivoted thin QR of every matrix of A (batch, m, n), m >= n, through qr_thin_pivoted_batched: returns Q (batch, m, n),
+    R (batch, n, n) and jpvt (batch, n; 0-based) with A[q][:, jpvt[q]] = Q[q] R[q]"""
+    At = _packed_batch(A, "qr_pivoted_batched")
+    batch, n, m = At.shape
+    Q = np.empty((batch, n, m))
+    R = np.empty((batch, n, n))
+    jpvt = np.zeros((max(batch, 1), max(n, 1)), dtype=np.intc)
+    check(lib.qr_thin_pivoted_batched(_p(At), m, n, batch, _p(Q), _p(R), jpvt.ctypes.data_as(_ip)), "qr_thin_pivoted_batched")
+    return Q.transpose(0, 2, 1), R.transpose(0, 2, 1), jpvt[:batch, :n].astype(np.int64)
+
+
+def lstsq_pivoted_batched(A, B, rcond=None, minnorm=True):
+    """rank-deficient least squares for every matrix of A (batch, m, n) and B (batch, m, nrhs) through qr_lstsq_pivoted_batched: returns
+    (X, resid, rank, jpvt) with X (batch, n, nrhs) the minimum-norm solutions (minnorm=False: the basic ones, zero outside the leading
+    rank columns of A P), resid[q, j] = ||A_q x_j - b_j||, rank (batch,) and jpvt (batch, n).  rcond None: max(m, n) eps.  No rank
+    raises."""
+    At = _packed_batch(A, "lstsq_pivoted_batched")
+    Bt = _packed_batch(B, "lstsq_pivoted_batched")
+    batch, n, m = At.shape
+    if Bt.shape[0] != batch or Bt.shape[2] != m:
+        raise QRError(f"lstsq_pivoted_batched: B is {Bt.shape[0]} matrices of {Bt.shape[2]} rows, A is {batch} of {m}", QR_E_ARG)
+    nrhs = Bt.shape[1]
+    X = np.empty((batch, nrhs, n))
+    resid = np.empty((batch, nrhs))
+    rank = np.zeros(max(batch, 1), dtype=np.intc)
+    jpvt = np.zeros((max(batch, 1), max(n, 1)), dtype=np.intc)
+    check(lib.qr_lstsq_pivoted_batched(_p(At), m, n, _p(Bt), nrhs, batch, -1.0 if rcond is None else float(rcond), int(bool(minnorm)),
+                                       _p(X), _p(resid), rank.ctypes.data_as(_ip), jpvt.ctypes.data_as(_ip)), "qr_lstsq_pivoted_batched")
+    return X.transpose(0, 2, 1), resid, rank[:batch].astype(np.int64), jpvt[:batch, :n].astype(np.int64)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -813,6 +851,34 @@ class Plan:
         """dgels per matrix: dA factored in place, rows 0..n-1 of dB_q <- X_q; dinfo (batch device ints): 0 or the first zero pivot + 1"""
         check(lib.qr_gels_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, _dptr(dB), nrhs, ldb, strideB,
                                       _dptr(dinfo), batch), "qr_gels_batched_dev")
+
+    def geqp3_batched(self, dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, batch):
+        """dgeqp3 of `batch` small matrices in place: the layout of geqrf_batched, djpvt (int32, n per matrix, 0-based) <- the permutation"""
+        check(lib.qr_geqp3_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(djpvt), stridejpvt, _dptr(dtau), stridetau, batch),
+              "qr_geqp3_batched_dev")
+
+    def rank_batched(self, dA, m, n, lda, strideA, drank, batch, rcond=None):
+        """drank (batch device int32) <- the rank of every matrix factored by geqp3_batched; queued, no host wait.  rcond None: max(m, n) eps"""
+        check(lib.qr_rank_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, -1.0 if rcond is None else float(rcond), _dptr(drank), batch),
+              "qr_rank_batched_dev")
+
+    def _gelsx_batched(self, name, dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dB, nrhs, ldb, strideB, rcond, dresid, drank,
+                       batch):
+        check(getattr(lib, name)(self.h, _dptr(dA), m, n, lda, strideA, _dptr(djpvt), stridejpvt, _dptr(dtau), stridetau, _dptr(dB), nrhs,
+                                 ldb, strideB, -1.0 if rcond is None else float(rcond), _dptr(dresid), _dptr(drank), batch), name)
+
+    def gelsp_batched(self, dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dB, nrhs, ldb, strideB, batch, rcond=None,
+                      dresid=None, drank=None):
+        """rank-deficient least squares per matrix, the basic solution: rows 0..n-1 of dB_q <- X_q (zero outside the leading rank columns
+        of A P); dresid (nrhs per matrix) and drank (batch int32) may be None"""
+        self._gelsx_batched("qr_gelsp_batched_dev", dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dB, nrhs, ldb, strideB,
+                            rcond, dresid, drank, batch)
+
+    def gelsy_batched(self, dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dB, nrhs, ldb, strideB, batch, rcond=None,
+                      dresid=None, drank=None):
+        """the same, the minimum-norm solution (LAPACK dgelsy)"""
+        self._gelsx_batched("qr_gelsy_batched_dev", dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dB, nrhs, ldb, strideB,
+                            rcond, dresid, drank, batch)
 
     def gesvj(self, jobv, dG, r, n, ldg, dS, dV=None, ldv=0):
         """dgesvj on the device: dG (r x n) <- the left singular vectors, dS <- the values (descending), dV (jobv 'V') <- the right ones;

@@ -5,12 +5,16 @@
  *   qr_gels_batched_dev    one fused launch while n + nrhs columns fit the kernel (the right-hand sides ride along as columns that are
  *                          updated but never factored, the back substitution runs in the same kernel); else geqrf, ormqr 'T', qrd_b_trsm
  *   qr_thin_batched, qr_lstsq_batched   the same on host pointers, packed batches
+ *   section 8b, column pivoting: qr_geqp3_batched_dev and qr_rank_batched_dev are one launch each (qrd_b_geqp3, qrd_b_rank);
+ *                          qr_gelsp_batched_dev / qr_gelsy_batched_dev route as qr_gels_batched_dev does: fused, else geqp3, ormqr 'T',
+ *                          qrd_b_solve_piv; qr_thin_pivoted_batched, qr_lstsq_pivoted_batched on host pointers
  *
  * The plan supplies the stream; its shape does not bound m and n.  Nothing here waits on the host except the host-pointer twins.
  *
  * Kept out of qr_host.c for the reason qr_solve.c is: the sanitizer and stub builds compile qr_host.c against a stub device layer that
  * has none of the launch wrappers called here. */
 #define _POSIX_C_SOURCE 200809L
+#include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -141,6 +145,130 @@ int qr_lstsq_batched(const double* A, int m, int n, const double* B, int nrhs, i
         }
     free(C);
     if (dinfo) qrd_free(dinfo);
+    if (d) qrd_free(d);
+    qr_plan_destroy(p);
+    return rc;
+}
+
+/* ---- section 8b: column pivoting ---- */
+
+static double eff_rcond(double rcond, int m, int n) { return rcond < 0.0 ? (double) (m > n ? m : n) * DBL_EPSILON : rcond; }
+
+int qr_geqp3_batched_dev(qr_plan* p, double* dA, int m, int n, int lda, long long strideA, int* djpvt, long long stridejpvt, double* dtau,
+                         long long stridetau, int batch)
+{
+    if (!p || !dA || !djpvt || !dtau || bad_shape(m, n, lda, strideA, stridetau, batch) || stridejpvt < n) return QR_E_ARG;
+    if (batch == 0) return 0;
+    return qrd_b_geqp3(p->stream, dA, m, n, lda, (size_t) strideA, djpvt, (size_t) stridejpvt, dtau, (size_t) stridetau, NULL, 0, 0, 0, 0.0, 0,
+                       NULL, NULL, batch);
+}
+
+int qr_rank_batched_dev(qr_plan* p, const double* dA, int m, int n, int lda, long long strideA, double rcond, int* drank, int batch)
+{
+    if (!p || !dA || !drank || rcond != rcond || bad_shape(m, n, lda, strideA, n, batch)) return QR_E_ARG;
+    if (batch == 0) return 0;
+    return qrd_b_rank(p->stream, dA, n, lda, (size_t) strideA, eff_rcond(rcond, m, n), drank, batch);
+}
+
+static int gelsx_batched(qr_plan* p, double* dA, int m, int n, int lda, long long strideA, int* djpvt, long long stridejpvt, double* dtau,
+                         long long stridetau, double* dB, int nrhs, int ldb, long long strideB, double rcond, double* dresid, int* drank,
+                         int batch, int minnorm)
+{
+    if (!p || !dA || !djpvt || !dtau || !dB || rcond != rcond || bad_shape(m, n, lda, strideA, stridetau, batch) || stridejpvt < n ||
+        bad_block(m, nrhs, ldb, strideB))
+        return QR_E_ARG;
+    if (batch == 0) return 0;
+    const size_t sa = (size_t) strideA, sj = (size_t) stridejpvt, st = (size_t) stridetau, sb = (size_t) strideB;
+    const double rc = eff_rcond(rcond, m, n);
+    if (nrhs <= QR_BATCHED_MAX_N - n && m <= qrd_b_max_rows(n + nrhs))      /* fused: [A | B] in one kernel */
+        return qrd_b_geqp3(p->stream, dA, m, n, lda, sa, djpvt, sj, dtau, st, dB, nrhs, ldb, sb, rc, minnorm, dresid, drank, batch);
+    CHECK(qrd_b_geqp3(p->stream, dA, m, n, lda, sa, djpvt, sj, dtau, st, NULL, 0, 0, 0, 0.0, 0, NULL, NULL, batch));
+    CHECK(qrd_b_ormqr(p->stream, 1, dA, m, n, lda, sa, dtau, st, dB, nrhs, ldb, sb, batch));
+    return qrd_b_solve_piv(p->stream, dA, m, n, lda, sa, djpvt, sj, dB, nrhs, ldb, sb, rc, minnorm, dresid, drank, batch);
+}
+
+int qr_gelsp_batched_dev(qr_plan* p, double* dA, int m, int n, int lda, long long strideA, int* djpvt, long long stridejpvt, double* dtau,
+                         long long stridetau, double* dB, int nrhs, int ldb, long long strideB, double rcond, double* dresid, int* drank,
+                         int batch)
+{
+    return gelsx_batched(p, dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dB, nrhs, ldb, strideB, rcond, dresid, drank, batch, 0);
+}
+
+int qr_gelsy_batched_dev(qr_plan* p, double* dA, int m, int n, int lda, long long strideA, int* djpvt, long long stridejpvt, double* dtau,
+                         long long stridetau, double* dB, int nrhs, int ldb, long long strideB, double rcond, double* dresid, int* drank,
+                         int batch)
+{
+    return gelsx_batched(p, dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dB, nrhs, ldb, strideB, rcond, dresid, drank, batch, 1);
+}
+
+int qr_thin_pivoted_batched(const double* A, int m, int n, int batch, double* Q, double* R, int* jpvt)
+{
+    if (!A || !Q || !R || !jpvt || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || batch < 0) return QR_E_ARG;
+    if (batch == 0) return 0;
+    const size_t mn = (size_t) m * n, nb = (size_t) batch;
+    qr_plan* p = NULL;
+    CHECK(qr_plan_create(&p, m, n, 0, 0));
+    double* d = NULL;
+    int* dj = NULL;
+    double *dA = NULL, *dQ = NULL, *dtau = NULL;
+    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (2 * mn + (size_t) n));
+    if (!rc) { dA = d; dQ = d + nb * mn; dtau = dQ + nb * mn; }
+    if (!rc) rc = qrd_malloc((void**) &dj, sizeof(int) * nb * (size_t) n);
+    double* F = (double*) malloc(sizeof(double) * nb * mn);
+    if (!rc && !F) rc = QR_E_ALLOC;
+    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
+    if (!rc) rc = qr_geqp3_batched_dev(p, dA, m, n, m, (long long) mn, dj, n, dtau, n, batch);
+    if (!rc) rc = qr_orgqr_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dQ, m, (long long) mn, batch);
+    if (!rc) rc = qrd_d2h(p->stream, Q, dQ, sizeof(double) * nb * mn);
+    if (!rc) rc = qrd_d2h(p->stream, F, dA, sizeof(double) * nb * mn);
+    if (!rc) rc = qrd_d2h(p->stream, jpvt, dj, sizeof(int) * nb * (size_t) n);
+    const int rs = qrd_stream_sync(p->stream);
+    if (!rc) rc = rs;
+    if (!rc)
+        for (size_t q = 0; q < nb; ++q)
+            for (int c = 0; c < n; ++c)
+                for (int r = 0; r < n; ++r) R[q * n * n + (size_t) c * n + r] = r <= c ? F[q * mn + (size_t) c * m + r] : 0.0;
+    free(F);
+    if (dj) qrd_free(dj);
+    if (d) qrd_free(d);
+    qr_plan_destroy(p);
+    return rc;
+}
+
+int qr_lstsq_pivoted_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, double rcond, int minnorm, double* X,
+                             double* resid, int* rank, int* jpvt)
+{
+    if (!A || !B || !X || rcond != rcond || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || nrhs < 1 || batch < 0)
+        return QR_E_ARG;
+    if (batch == 0) return 0;
+    const size_t mn = (size_t) m * n, mr = (size_t) m * nrhs, nb = (size_t) batch;
+    qr_plan* p = NULL;
+    CHECK(qr_plan_create(&p, m, n, 0, 0));
+    double* d = NULL;
+    int* di = NULL;
+    int *dj = NULL, *drank = NULL;
+    double *dA = NULL, *dB = NULL, *dtau = NULL, *dres = NULL;
+    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (mn + mr + (size_t) n + (size_t) nrhs));
+    if (!rc) { dA = d; dB = d + nb * mn; dtau = dB + nb * mr; dres = dtau + nb * (size_t) n; }
+    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * ((size_t) n + 1));
+    if (!rc) { dj = di; drank = di + nb * (size_t) n; }
+    double* C = (double*) malloc(sizeof(double) * nb * mr);
+    if (!rc && !C) rc = QR_E_ALLOC;
+    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
+    if (!rc) rc = qrd_h2d(p->stream, dB, B, sizeof(double) * nb * mr);
+    if (!rc)
+        rc = gelsx_batched(p, dA, m, n, m, (long long) mn, dj, n, dtau, n, dB, nrhs, m, (long long) mr, rcond, dres, drank, batch, minnorm != 0);
+    if (!rc) rc = qrd_d2h(p->stream, C, dB, sizeof(double) * nb * mr);
+    if (!rc && resid) rc = qrd_d2h(p->stream, resid, dres, sizeof(double) * nb * (size_t) nrhs);
+    if (!rc && rank) rc = qrd_d2h(p->stream, rank, drank, sizeof(int) * nb);
+    if (!rc && jpvt) rc = qrd_d2h(p->stream, jpvt, dj, sizeof(int) * nb * (size_t) n);
+    const int rs = qrd_stream_sync(p->stream);
+    if (!rc) rc = rs;
+    if (!rc)
+        for (size_t q = 0; q < nb; ++q)
+            for (int j = 0; j < nrhs; ++j) memcpy(X + (q * nrhs + j) * n, C + q * mr + (size_t) j * m, sizeof(double) * (size_t) n);
+    free(C);
+    if (di) qrd_free(di);
     if (d) qrd_free(d);
     qr_plan_destroy(p);
     return rc;

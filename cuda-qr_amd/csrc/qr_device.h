@@ -281,6 +281,16 @@ int qrd_b_ormqr(void* stream, int trans_t, const double* A, int m, int n, int ld
                 double* Cm, int nrhs, int ldc, size_t strideC, int batch);
 int qrd_b_eye(void* stream, double* Q, int m, int n, int ldq, size_t strideQ, int batch);
 int qrd_b_trsm(void* stream, const double* A, int n, int lda, size_t strideA, double* B, int nrhs, int ldb, size_t strideB, int* info, int batch);
+/* the same with column pivoting (mi355x_qr.h section 8b; the same two routes, chosen the same way).
+ * qrd_b_geqp3: dlaqp2 of every A, jpvt 0-based; nrhs > 0 (the fused gelsp / gelsy): B's columns ride along, then the rank r (the leading
+ * run of |R(i,i)| > rcond |R(0,0)|, rcond >= 0), resid[q * nrhs + j] = |(Q^T b_j)(r..m)| and rank[q] (either may be NULL), and X in the
+ * caller's column order in rows 0..n-1 of B (minnorm != 0: through [R11 R12] = [T11 0] Z), all in the one launch.
+ * qrd_b_rank: rank[q] from the diagonal of R.  qrd_b_solve_piv: rank, resid and X from factors and Q^T B (the composed route). */
+int qrd_b_geqp3(void* stream, double* A, int m, int n, int lda, size_t strideA, int* jpvt, size_t stridej, double* tau, size_t stridetau,
+                double* B, int nrhs, int ldb, size_t strideB, double rcond, int minnorm, double* resid, int* rank, int batch);
+int qrd_b_rank(void* stream, const double* A, int n, int lda, size_t strideA, double rcond, int* rank, int batch);
+int qrd_b_solve_piv(void* stream, const double* A, int m, int n, int lda, size_t strideA, const int* jpvt, size_t stridej, double* B, int nrhs,
+                    int ldb, size_t strideB, double rcond, int minnorm, double* resid, int* rank, int batch);
 
 #define QRD_LEAFW 32
 

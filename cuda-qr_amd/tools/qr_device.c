@@ -33,6 +33,11 @@
  * `./qr_device m n --batched count` does nothing else either: `count` seeded m x n matrices are factored in one qr_geqrf_batched_dev
  * call (batch resident in HBM), Q formed by qr_orgqr_batched_dev: the time of the factorisation and the worst backward error
  * ||A - Q R||_F / ||A||_F and orthogonality error ||Q^T Q - I||_F over the batch (products formed on the host).
+ *
+ * `./qr_device m n --batched count --pivot [rank]` does nothing else either: `count` seeded m x n matrices of that rank (products of
+ * m x rank and rank x n factors; default n) and one right-hand side each go through one qr_gelsy_batched_dev call: the time, the
+ * smallest and largest rank found, and the worst ||A^T (A x - b)|| / (||A||_F^2 ||x|| + ||A||_F ||b||) over the batch (zero at a
+ * least-squares solution; formed on the host).
  */
 #include <math.h>
 #include <stdio.h>
@@ -457,9 +462,99 @@ static int batched_main(int m, int n, int count)
     return 0;
 }
 
+/* count matrices of m x n and of rank `rank` through one pivoted least-squares call */
+static int batched_pivot_main(int m, int n, int count, int rank)
+{
+    if (n < 1 || n > QR_BATCHED_MAX_N || m < n || count < 1 || rank < 1 || rank > n) {
+        fprintf(stderr, "--batched count --pivot [rank] needs count >= 1, 1 <= rank <= n <= %d, n <= m\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d matrices of %dx%d, rank %d\n", count, m, n, rank);
+    const size_t mn = (size_t) m * n, cnt = mn * count;
+    double *A = malloc(sizeof(double) * cnt), *B = malloc(sizeof(double) * (size_t) m * count), *X = malloc(sizeof(double) * (size_t) m * count);
+    double *U = malloc(sizeof(double) * (size_t) m * rank), *W = malloc(sizeof(double) * (size_t) rank * n);
+    int* rk = malloc(sizeof(int) * (size_t) count);
+    if (!A || !B || !X || !U || !W || !rk) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (int q = 0; q < count; q++) {
+        double* a = A + q * mn;
+        if (rank == n) {
+            for (size_t i = 0; i < mn; i++) a[i] = (double) rand() / RAND_MAX - 0.5;
+        } else {
+            for (size_t i = 0; i < (size_t) m * rank; i++) U[i] = (double) rand() / RAND_MAX - 0.5;
+            for (size_t i = 0; i < (size_t) rank * n; i++) W[i] = (double) rand() / RAND_MAX - 0.5;
+            for (int j = 0; j < n; j++)
+                for (int i = 0; i < m; i++) {
+                    double s = 0.0;
+                    for (int k = 0; k < rank; k++) s += U[(size_t) k * m + i] * W[(size_t) j * rank + k];
+                    a[(size_t) j * m + i] = s;
+                }
+        }
+        for (int i = 0; i < m; i++) B[(size_t) q * m + i] = (double) rand() / RAND_MAX - 0.5;
+    }
+    qr_plan* p = NULL;
+    double *dA = NULL, *dB = NULL, *dtau = NULL;
+    int *dj = NULL, *drank = NULL;
+    if (qr_plan_create(&p, m, n, 0, 0) || qr_device_malloc((void**) &dA, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dB, sizeof(double) * (size_t) m * count) || qr_device_malloc((void**) &dtau, sizeof(double) * (size_t) n * count) ||
+        qr_device_malloc((void**) &dj, sizeof(int) * (size_t) n * count) || qr_device_malloc((void**) &drank, sizeof(int) * (size_t) count)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dA, A, sizeof(double) * cnt) || qr_copy_to_device(dB, B, sizeof(double) * (size_t) m * count)) {
+            fprintf(stderr, "copy failed\n");
+            return 1;
+        }
+        const double t0 = now();
+        int rc = qr_gelsy_batched_dev(p, dA, m, n, m, (long long) mn, dj, n, dtau, n, dB, 1, m, m, -1.0, NULL, drank, count);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc) {
+            fprintf(stderr, "qr_gelsy_batched_dev failed: %s%s\n", qr_strerror(rc), rc == QR_E_ARG ? " (the matrix does not fit the LDS: see qr_batched_max_rows)" : "");
+            return 1;
+        }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(X, dB, sizeof(double) * (size_t) m * count) || qr_copy_to_host(rk, drank, sizeof(int) * (size_t) count)) {
+        fprintf(stderr, "copy back failed\n");
+        return 1;
+    }
+    int rmin = rk[0], rmax = rk[0];
+    double worst = 0.0;
+    for (int q = 0; q < count; q++) {
+        const double *a = A + q * mn, *b = B + (size_t) q * m, *x = X + (size_t) q * m;
+        if (rk[q] < rmin) rmin = rk[q];
+        if (rk[q] > rmax) rmax = rk[q];
+        double na = 0.0, nx = 0.0, nb = 0.0, ng = 0.0;
+        for (size_t i = 0; i < mn; i++) na += a[i] * a[i];
+        for (int j = 0; j < n; j++) nx += x[j] * x[j];
+        for (int i = 0; i < m; i++) nb += b[i] * b[i];
+        for (int i = 0; i < m; i++) {         /* U's first m entries as scratch: the residual A x - b */
+            double s = -b[i];
+            for (int j = 0; j < n; j++) s += a[(size_t) j * m + i] * x[j];
+            U[i] = s;
+        }
+        for (int j = 0; j < n; j++) {
+            double s = 0.0;
+            for (int i = 0; i < m; i++) s += a[(size_t) j * m + i] * U[i];
+            ng += s * s;
+        }
+        const double den = na * sqrt(nx) + sqrt(na) * sqrt(nb);
+        if (den > 0.0 && sqrt(ng) / den > worst) worst = sqrt(ng) / den;
+    }
+    printf(" MMQR ran pivoted least squares on %d %dx%d matrices in %f s (avg over %d)   [batch resident in HBM, one right-hand side each]\n", count,
+           m, n, el / TRIALS, TRIALS);
+    printf(" ranks found: %d .. %d (built with rank %d)   worst ||A^T (A x - b)|| / (||A||^2 ||x|| + ||A|| ||b||) = %.2e\n", rmin, rmax, rank, worst);
+    qr_device_free(dA); qr_device_free(dB); qr_device_free(dtau); qr_device_free(dj); qr_device_free(drank);
+    qr_plan_destroy(p);
+    free(A); free(B); free(X); free(U); free(W); free(rk);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank]]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -471,6 +566,10 @@ int main(int argc, char** argv)
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--batched") == 0) {
             if (i + 1 >= argc) { fprintf(stderr, "--batched needs a count\n"); return 1; }
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--pivot") == 0)
+                    return batched_pivot_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]),
+                                              k + 1 < argc && argv[k + 1][0] != '-' ? atoi(argv[k + 1]) : atoi(argv[2]));
             return batched_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
         }
     for (int i = 3; i < argc; i++)

@@ -672,6 +672,60 @@ int qr_thin_batched(const double* A, int m, int n, int batch, double* Q, double*
 int qr_lstsq_batched(const double* A, int m, int n, const double* B, int nrhs, int batch,
                      double* X, double* resid, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8b. Batched column-pivoted QR and rank-deficient least squares: section 8 for batches in which some matrix may be rank-deficient (a
+ * constant regressor, a duplicated feature, fewer distinct samples than unknowns).  Section 8's conventions hold unchanged: the layout
+ * (base + q * stride, column-major, strides in elements: doubles for dA, dtau, dB, ints for djpvt), the shape limits
+ * (n <= QR_BATCHED_MAX_N, m as qr_batched_max_rows describes), the plan that supplies the stream only, no host wait, QR_E_ARG for bad
+ * arguments before anything touches a device (djpvt NULL, stridejpvt < n and a NaN rcond among them), batch == 0 returns 0, no atomics, every sum in
+ * a fixed order, results bitwise repeatable and bitwise independent of `batch` and of a matrix's index.
+ *
+ * The factorisation is LAPACK dgeqp3 with every column free (its unblocked kernel dlaqp2) per matrix, A P = Q R: at step j the
+ * remaining column of largest partial norm is swapped in, the lowest index on a tie; the partial norms are downdated by
+ * vn1 *= sqrt(max(0, 1 - (|A(j,c)| / vn1)^2)) and recomputed from rows j+1..m-1 when that estimate times (vn1 / vn2)^2 is at most
+ * sqrt(eps).  The matrix is in registers or LDS throughout, so norms, arg-max and swap never touch memory: one launch whatever `batch`
+ * is.  The rank of a factored matrix is the length of the leading run of |R(i,i)| > rcond |R(0,0)|; rcond < 0 selects
+ * max(m, n) * DBL_EPSILON; a zero matrix has rank 0.
+ * ------------------------------------------------------------------------------------------- */
+
+/* dgeqp3 of every matrix in place.  dA comes back in the layout of qr_geqrf_batched_dev (R, V, dlarfg signs, tau = 0 for a column with
+ * nothing below it), so qr_ormqr_batched_dev and qr_orgqr_batched_dev apply to it unchanged.  djpvt: n ints per matrix, 0-based: column
+ * j of A P is column djpvt[j] of the caller's matrix. */
+int qr_geqp3_batched_dev(qr_plan* plan, double* dA, int m, int n, int lda, long long strideA,
+                         int* djpvt, long long stridejpvt, double* dtau, long long stridetau, int batch);
+
+/* drank[q] (batch device ints) = the rank of matrix q from the factors of qr_geqp3_batched_dev, written in stream order: unlike
+ * qr_rank_dev this call does not wait for the device. */
+int qr_rank_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda, long long strideA,
+                        double rcond, int* drank, int batch);
+
+/* Rank-deficient least squares per matrix: factor with pivoting, r = the rank as above, X into rows 0..n-1 of dB in the caller's column
+ * order.  qr_gelsp_batched_dev gives the basic solution (section 4's meaning: X(jpvt[0..r), :) = R11^-1 (Q^T B)(0..r, :), every other row
+ * exactly 0.0); qr_gelsy_batched_dev the minimum-norm one (LAPACK dgelsy, what numpy.linalg.lstsq returns): [R11 R12] = [T11 0] Z by r
+ * reflectors from the right (dtzrzf), X = P Z^T [T11^-1 (Q^T B)(0..r, :); 0].  With r == n the two give the same bits.
+ * Rows n..m-1 of dB hold the tail of Q^T B as in qr_gels_batched_dev; dresid (nrhs doubles per matrix, packed, may be NULL) =
+ * ||(Q^T b_j)(r..m)||_2 = ||A x_j - b_j||_2; drank (batch ints, may be NULL) = r.  dA, dtau and djpvt come back as
+ * qr_geqp3_batched_dev leaves them; Z is not returned.  Singularity is never an error: a zero matrix gives rank 0 and X = 0.
+ * One fused launch when n + nrhs <= QR_BATCHED_MAX_N and m <= qr_batched_max_rows(n + nrhs) (the right-hand sides ride along as
+ * columns that are updated but never pivoted or factored); otherwise geqp3, ormqr 'T' and a batched solve (three launches). */
+int qr_gelsp_batched_dev(qr_plan* plan, double* dA, int m, int n, int lda, long long strideA,
+                         int* djpvt, long long stridejpvt, double* dtau, long long stridetau,
+                         double* dB, int nrhs, int ldb, long long strideB,
+                         double rcond, double* dresid, int* drank, int batch);
+int qr_gelsy_batched_dev(qr_plan* plan, double* dA, int m, int n, int lda, long long strideA,
+                         int* djpvt, long long stridejpvt, double* dtau, long long stridetau,
+                         double* dB, int nrhs, int ldb, long long strideB,
+                         double rcond, double* dresid, int* drank, int batch);
+
+/* The pivoted twin of qr_thin_batched: A[:, jpvt] = Q R per matrix, jpvt n ints per matrix (0-based).  Synchronous. */
+int qr_thin_pivoted_batched(const double* A, int m, int n, int batch, double* Q, double* R, int* jpvt);
+
+/* Rank-deficient least squares on a packed batch on host pointers (A and B untouched): X n x nrhs per matrix, minimum-norm (minnorm
+ * != 0, gelsy) or basic (gelsp); resid (nrhs per matrix), rank (batch ints) and jpvt (n per matrix) may each be NULL.  Creates a plan of
+ * its own.  Synchronous.  Returns 0 for any rank. */
+int qr_lstsq_pivoted_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, double rcond, int minnorm,
+                             double* X, double* resid, int* rank, int* jpvt);
+
 #ifdef __cplusplus
 }
 #endif
