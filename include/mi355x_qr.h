@@ -431,7 +431,8 @@ int qr_tpqrt_max_rows(void);
  * LAPACK dlarfg per column: beta = -sign(R(j,j)) hypot(R(j,j), |B(:,j)|); a column of B that is exactly zero gives tau = 0 and leaves
  * everything untouched, so R = 0 on entry is legal (that is how an accumulation starts); exact zeros in B stay exact zeros, so a caller
  * may hand over an upper-triangular block with explicit zeros and get V of the same shape.  (dlarfg's rescaling of subnormal columns
- * is not reproduced.)  Two launches per QR_TPQRT_PANEL columns. */
+ * is not reproduced.  Tested range, this section and 6b: bitwise equivariant under scaling [R ; B] by 2^-299 .. 2^301, and at 2^+-480
+ * -- entries of about 1e+-144 -- the Gram identity holds as for entries of order one, tests/test_gpu_range_edges.py.)  Two launches per QR_TPQRT_PANEL columns. */
 int qr_tpqrt_dev(qr_plan* plan, double* dR, int n, int ldr, double* dB, int p, int ldb, double* dT, int ldt);
 
 /* LAPACK dtpmqrt (side 'L', L = 0): [C1 ; C2] <- Q'^T [C1 ; C2] (trans 'T') or Q' [C1 ; C2] ('N') with dV, dT from qr_tpqrt_dev;
@@ -550,7 +551,9 @@ int qr_lstsq_rolling(const double* A, long long m, int n, int lda, const double*
  * Accuracy is that of the QR itself: values to n eps of the largest, norm-wise.  Two columns whose norms differ by more than a factor
  * DBL_EPSILON are not rotated against each other (the smaller one cannot change the larger by an ulp): that is what lets an exactly
  * rank-deficient input converge, and it is why values below eps times their neighbours' carry no relative accuracy.  Column norms are plain sums of squares (dgesvj's
- * rescaling against over- and underflow is not reproduced).
+ * rescaling against over- and underflow is not reproduced).  Tested range: U, V, the sweep count and sigma / s are bitwise the same for
+ * an input scaled by s = 2^-299 .. 2^301, and at s = 2^+-480 (entries of about 1e+-144) reconstruction and orthogonality stay within
+ * sweeps * n * eps (tests/test_gpu_scale_equivariance.py, tests/test_gpu_range_edges.py); beyond that the squares leave the normal range.
  * Out of scope: m < n (transpose with qr_transpose_dev and swap the roles of U and V); a qr_geqp3_dev-preconditioned variant for high
  * RELATIVE accuracy of tiny singular values (dgejsv's); a multi-GPU driver (it follows from qr_tsqr_factor_dev's R and is a later change).
  * ------------------------------------------------------------------------------------------- */

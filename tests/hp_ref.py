@@ -1,0 +1,241 @@
+"""A plain extended-precision reference for the factor and solve paths (helper module, no fixtures, no GPU).
+
+Everything is written as straight loops over columns in numpy, without LAPACK, and is parameterised by dtype: the `longdouble`
+instance (64-bit significand) is the reference, the `float64` instance of the very same code is "the same operation in working precision"
+that the GPU tests measure the kernels' errors against.  The Householder convention is LAPACK's dgeqr2 / dlarfg (beta = -sign(alpha)
+||x||, tau = (beta - alpha) / beta, v = x / (alpha - beta) with a unit head, an exactly zero tail gives tau = 0) without dlarfg's
+rescaling of tiny vectors.  Sums of squares are plain `(x * x).sum()`: for a power of two s every function here is exactly
+homogeneous while nothing leaves the normal range, which tests/test_hp_ref.py asserts bitwise.
+"""
+import numpy as np
+
+LD = np.longdouble
+if np.finfo(LD).nmant < 63:          # a platform whose long double is a double: 40 decimal digits through mpmath objects instead
+    import mpmath
+
+    mpmath.mp.dps = 40
+    LD = np.dtype(object)
+    _lift = np.frompyfunc(mpmath.mpf, 1, 1)
+    _sqrt = np.frompyfunc(mpmath.sqrt, 1, 1)
+    EPS_LD = 10.0 ** -39
+else:
+    assert np.finfo(LD).nmant >= 63
+    _lift, _sqrt = None, np.sqrt
+    EPS_LD = float(np.finfo(LD).eps)
+EPS = float(np.finfo(np.float64).eps)
+
+
+def arr(A, dtype=LD):
+    """a fresh array of A's values in `dtype` (exact for float64 input)"""
+    A = np.asarray(A)
+    if dtype is LD and _lift is not None:
+        return _lift(np.asarray(A, dtype=np.float64)).astype(object)
+    return np.array(A, dtype=dtype)
+
+
+def _root(x, dtype):
+    return _sqrt(x) if (dtype is LD and _lift is not None) else np.sqrt(x)
+
+
+def norm(x, dtype=LD):
+    """Frobenius norm, accumulated in `dtype`"""
+    x = arr(x, dtype)
+    return _root((x * x).sum(), dtype)
+
+
+def _house(x, dtype):
+    """dlarfg on x (modified in place: x[0] <- beta, x[1:] <- v's tail); returns tau"""
+    alpha = x[0]
+    ssq = (x[1:] * x[1:]).sum() if x.size > 1 else 0
+    if ssq == 0:
+        return alpha * 0
+    nrm = _root(alpha * alpha + ssq, dtype)
+    beta = -nrm if alpha >= 0 else nrm
+    x[1:] = x[1:] / (alpha - beta)
+    x[0] = beta
+    return (beta - alpha) / beta
+
+
+def _reflect(v_tail, tau, C):
+    """C <- (I - tau v v^T) C with v = [1; v_tail], in place"""
+    if tau == 0 or C.shape[1] == 0:
+        return
+    w = C[0] + (v_tail[:, None] * C[1:]).sum(axis=0)
+    C[0] -= tau * w
+    C[1:] -= tau * v_tail[:, None] * w[None, :]
+
+
+def qr(A, dtype=LD):
+    """dgeqr2: (F, tau) with R in F's upper triangle and the tails of v below the diagonal"""
+    F = arr(A, dtype)
+    m, n = F.shape
+    k = min(m, n)
+    tau = arr(np.zeros(k), dtype)
+    for j in range(k):
+        tau[j] = _house(F[j:, j], dtype)
+        _reflect(F[j + 1:, j], tau[j], F[j:, j + 1:])
+    return F, tau
+
+
+def apply_q(F, tau, C, trans, dtype=LD):
+    """Q^T C (trans 'T') or Q C ('N') for the m x m Q of (F, tau); C has m rows"""
+    F, C = arr(F, dtype), arr(C, dtype)
+    if C.ndim == 1:
+        return apply_q(F, tau, C[:, None], trans, dtype)[:, 0]
+    tau = arr(tau, dtype)
+    k = len(tau)
+    for j in (range(k) if trans == "T" else range(k - 1, -1, -1)):
+        _reflect(F[j + 1:, j], tau[j], C[j:])
+    return C
+
+
+def form_q(F, tau, dtype=LD):
+    """the explicit thin Q (m x n)"""
+    m, n = np.shape(F)
+    return apply_q(F, tau, np.eye(m, min(m, n)), "N", dtype)
+
+
+def triu(F):
+    n = min(np.shape(F))
+    return np.triu(np.asarray(F)[:n, :n])
+
+
+def solve_r(R, B, dtype=LD):
+    """upper back substitution X = R^-1 B, column-oriented as dtrsm's"""
+    R, X = arr(R, dtype), arr(B, dtype)
+    vec = X.ndim == 1
+    X = X[:, None] if vec else X
+    for i in range(R.shape[0] - 1, -1, -1):
+        X[i] = X[i] / R[i, i]
+        X[:i] -= R[:i, i][:, None] * X[i][None, :]
+    return X[:, 0] if vec else X
+
+
+def solve_rt(R, B, dtype=LD):
+    """forward substitution X = R^-T B"""
+    R, X = arr(R, dtype), arr(B, dtype)
+    vec = X.ndim == 1
+    X = X[:, None] if vec else X
+    n = R.shape[0]
+    for i in range(n):
+        X[i] = X[i] / R[i, i]
+        X[i + 1:] -= R[i, i + 1:][:, None] * X[i][None, :]
+    return X[:, 0] if vec else X
+
+
+def lstsq(A, B, dtype=LD):
+    """min ||A X - B|| for a full-rank tall A: (X, residual norms per column)"""
+    F, tau = qr(A, dtype)
+    n = F.shape[1]
+    B = arr(B, dtype)
+    vec = B.ndim == 1
+    Y = apply_q(F, tau, B[:, None] if vec else B, "T", dtype)
+    X = solve_r(triu(F), Y[:n], dtype)
+    res = _root((Y[n:] * Y[n:]).sum(axis=0), dtype)
+    return (X[:, 0], res[0]) if vec else (X, res)
+
+
+def minnorm(A, B, dtype=LD):
+    """the minimum-norm solution of A X = B for a full-rank wide A (m <= n): X = Q [R^-T B ; 0] with A^T = Q R"""
+    A = arr(A, dtype)
+    m, n = A.shape
+    F, tau = qr(A.T, dtype)
+    B = arr(B, dtype)
+    vec = B.ndim == 1
+    Y = arr(np.zeros((n, 1 if vec else B.shape[1])), dtype)
+    Y[:m] = solve_rt(triu(F), B[:, None] if vec else B, dtype)
+    X = apply_q(F, tau, Y, "N", dtype)
+    return X[:, 0] if vec else X
+
+
+def append_rows(R, B, dtype=LD):
+    """(F, tau) of the QR of [R ; B]: R' in the upper triangle (the row-append update's result)"""
+    return qr(np.vstack([arr(triu(R), dtype), arr(B, dtype)]), dtype)
+
+
+def remove_rows(A, keep, dtype=LD):
+    """R of the rows of A that survive a removal (boolean mask or index list `keep`)"""
+    return triu(qr(arr(A, dtype)[keep], dtype)[0])
+
+
+def qrp(A, dtype=LD):
+    """greedy column-pivoted QR with dlaqp2's rule: (F, tau, jpvt 0-based).  The partial norms are downdated by
+    vn1 *= sqrt(max(0, 1 - (|F(j,c)| / vn1)^2)) and recomputed when that times (vn1 / vn2)^2 is at most sqrt(eps of float64); the
+    first maximum wins a tie."""
+    F = arr(A, dtype)
+    m, n = F.shape
+    k = min(m, n)
+    jpvt, tau = np.arange(n), arr(np.zeros(k), dtype)
+    vn1 = _root((F * F).sum(axis=0), dtype)
+    vn2 = vn1.copy()
+    tol3z = np.sqrt(EPS)
+    for j in range(k):
+        p = j + int(np.argmax(vn1[j:]))
+        if p != j:
+            F[:, [j, p]] = F[:, [p, j]]
+            jpvt[[j, p]] = jpvt[[p, j]]
+            vn1[p], vn2[p] = vn1[j], vn2[j]
+        tau[j] = _house(F[j:, j], dtype)
+        _reflect(F[j + 1:, j], tau[j], F[j:, j + 1:])
+        for c in range(j + 1, n):
+            if vn1[c] == 0:
+                continue
+            t = abs(F[j, c]) / vn1[c]
+            temp = max(t * 0, 1 - t * t)
+            r = vn1[c] / vn2[c]
+            if temp * r * r <= tol3z:
+                x = F[j + 1:, c]
+                vn1[c] = vn2[c] = _root((x * x).sum(), dtype) if x.size else t * 0
+            else:
+                vn1[c] = vn1[c] * _root(temp, dtype)
+    return F, tau, jpvt
+
+
+# ---- error measures, all evaluated in extended precision (inputs of any dtype) ------------------------------------------------------
+def trsm_backward_errors(R, X, B, trans=False):
+    """||op(R) x - b|| / (||R|| ||x|| + ||b||) of every column"""
+    R, X, B = arr(triu(R)), arr(X), arr(B)
+    X, B = (X[:, None], B[:, None]) if X.ndim == 1 else (X, B)
+    M = R.T if trans else R
+    nR = norm(R)
+    out = np.zeros(X.shape[1])
+    for j in range(X.shape[1]):
+        r = (M * X[:, j][None, :]).sum(axis=1) - B[:, j]
+        den = nR * norm(X[:, j]) + norm(B[:, j])
+        out[j] = float(norm(r) / den) if den != 0 else 0.0
+    return out
+
+
+def trsm_backward_error(R, X, B, trans=False):
+    """the worst column's"""
+    return float(trsm_backward_errors(R, X, B, trans).max())
+
+
+def matmul(A, B):
+    """A @ B in extended precision by outer products (no BLAS)"""
+    A, B = arr(A), arr(B)
+    out = arr(np.zeros((A.shape[0], B.shape[1])))
+    for k in range(A.shape[1]):
+        out += A[:, k][:, None] * B[k][None, :]
+    return out
+
+
+def apply_error(ref, out, C):
+    """||ref - out|| / ||C||"""
+    return float(norm(arr(ref) - arr(out)) / norm(C))
+
+
+def factor_errors(A, Q, R):
+    """(||A - Q R|| / ||A||, ||Q^T Q - I||) for a thin Q"""
+    A, Q, R = arr(A), arr(Q), arr(R)
+    n = Q.shape[1]
+    return float(norm(A - matmul(Q, R)) / norm(A)), float(norm(matmul(Q.T, Q) - arr(np.eye(n))))
+
+
+def normal_equations_residual(A, X, B):
+    """||A^T (A x - b)|| / (||A||^2 ||x|| + ||A|| ||b||), the worst column"""
+    A, X, B = arr(A), arr(X), arr(B)
+    X, B = (X[:, None], B[:, None]) if X.ndim == 1 else (X, B)
+    g = matmul(A.T, matmul(A, X) - B)
+    nA = norm(A)
+    return max(float(norm(g[:, j]) / (nA * nA * norm(X[:, j]) + nA * norm(B[:, j]))) for j in range(X.shape[1]))
