@@ -169,6 +169,9 @@ for _name in ("qr_gelsp_batched_dev", "qr_gelsy_batched_dev"):
     _sig(_name, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, C.c_double, _vp, _vp, C.c_int)
 _sig("qr_thin_pivoted_batched", C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip)
 _sig("qr_lstsq_pivoted_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _ip, _ip)
+_sig("qr_gesvd_batched_dev", C.c_int, _vp, C.c_char, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, C.c_int, _ll,
+     _vp, C.c_int, _ll, _vp, _vp, _vp, C.c_int)
+_sig("qr_svd_batched", C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -559,6 +562,24 @@ def lstsq_pivoted_batched(A, B, rcond=None, minnorm=True):
     return X.transpose(0, 2, 1), resid, rank[:batch].astype(np.int64), jpvt[:batch, :n].astype(np.int64)
 
 
+def svd_batched(A, compute_uv=True):
+    """the SVD of every matrix of A (batch, m, n), m >= n, through qr_svd_batched: returns (U, S, V, rank) with U (batch, m, n), S (batch, n)
+    descending, V (batch, n, n) -- V, not numpy's V^T -- and rank (batch,) = the number of non-zero values, A[q] = U[q] diag(S[q]) V[q]^T;
+    compute_uv False: U and V are None"""
+    At = _packed_batch(A, "svd_batched")
+    batch, n, m = At.shape
+    S = np.empty((batch, n))
+    rank = np.zeros(max(batch, 1), dtype=np.intc)
+    U = np.empty((batch, n, m)) if compute_uv else None
+    V = np.empty((batch, n, n)) if compute_uv else None
+    check(lib.qr_svd_batched(_p(At), m, n, batch, _p(S), _p(U) if compute_uv else None, _p(V) if compute_uv else None,
+                             rank.ctypes.data_as(_ip)), "qr_svd_batched")
+    rank = rank[:batch].astype(np.int64)
+    if not compute_uv:
+        return None, S, None, rank
+    return U.transpose(0, 2, 1), S, V.transpose(0, 2, 1), rank
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -879,6 +900,15 @@ class Plan:
         """the same, the minimum-norm solution (LAPACK dgelsy)"""
         self._gelsx_batched("qr_gelsy_batched_dev", dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dB, nrhs, ldb, strideB,
                             rcond, dresid, drank, batch)
+
+    def gesvd_batched(self, jobu, jobv, dA, m, n, lda, strideA, djpvt, stridejpvt, dtau, stridetau, dS, strideS, dinfo, batch, dU=None, ldu=0,
+                      strideU=0, dV=None, ldv=0, strideV=0, drank=None, dsweeps=None):
+        """the SVD of `batch` small matrices: dA, djpvt, dtau <- the factors of geqp3_batched; dS (n per matrix, descending); jobu 'U': dU
+        (m x n per matrix); jobv 'V': dV (n x n per matrix, V itself); drank, dsweeps (int32, optional); dinfo (int32): 1 where the sweep
+        limit was reached"""
+        check(lib.qr_gesvd_batched_dev(self.h, jobu.encode(), jobv.encode(), _dptr(dA), m, n, lda, strideA, _dptr(djpvt), stridejpvt,
+                                       _dptr(dtau), stridetau, _dptr(dS), strideS, _dptr(dU), ldu, strideU, _dptr(dV), ldv, strideV,
+                                       _dptr(drank), _dptr(dsweeps), _dptr(dinfo), batch), "qr_gesvd_batched_dev")
 
     def gesvj(self, jobv, dG, r, n, ldg, dS, dV=None, ldv=0):
         """dgesvj on the device: dG (r x n) <- the left singular vectors, dS <- the values (descending), dV (jobv 'V') <- the right ones;

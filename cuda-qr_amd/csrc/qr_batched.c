@@ -8,6 +8,8 @@
  *   section 8b, column pivoting: qr_geqp3_batched_dev and qr_rank_batched_dev are one launch each (qrd_b_geqp3, qrd_b_rank);
  *                          qr_gelsp_batched_dev / qr_gelsy_batched_dev route as qr_gels_batched_dev does: fused, else geqp3, ormqr 'T',
  *                          qrd_b_solve_piv; qr_thin_pivoted_batched, qr_lstsq_pivoted_batched on host pointers
+ *   section 8c, singular values: qr_gesvd_batched_dev is geqp3, qrd_b_jsvd (qr_batched_svd.hip: rank cut, Jacobi on R^T in LDS, V) and,
+ *                          when U is wanted, ormqr 'N' on [W; 0]: three launches, or two; qr_svd_batched on host pointers
  *
  * The plan supplies the stream; its shape does not bound m and n.  Nothing here waits on the host except the host-pointer twins.
  *
@@ -268,6 +270,73 @@ int qr_lstsq_pivoted_batched(const double* A, int m, int n, const double* B, int
         for (size_t q = 0; q < nb; ++q)
             for (int j = 0; j < nrhs; ++j) memcpy(X + (q * nrhs + j) * n, C + q * mr + (size_t) j * m, sizeof(double) * (size_t) n);
     free(C);
+    if (di) qrd_free(di);
+    if (d) qrd_free(d);
+    qr_plan_destroy(p);
+    return rc;
+}
+
+/* ---- section 8c: singular value decomposition ---- */
+
+static int bad_job(char job, char yes) { return job != yes && job != 'N'; }
+
+int qr_gesvd_batched_dev(qr_plan* p, char jobu, char jobv, double* dA, int m, int n, int lda, long long strideA, int* djpvt,
+                         long long stridejpvt, double* dtau, long long stridetau, double* dS, long long strideS, double* dU, int ldu,
+                         long long strideU, double* dV, int ldv, long long strideV, int* drank, int* dsweeps, int* dinfo, int batch)
+{
+    if (!p || !dA || !djpvt || !dtau || !dS || !dinfo || bad_job(jobu, 'U') || bad_job(jobv, 'V') ||
+        bad_shape(m, n, lda, strideA, stridetau, batch) || stridejpvt < n || strideS < n)
+        return QR_E_ARG;
+    if (jobu == 'U' && (!dU || bad_block(m, n, ldu, strideU))) return QR_E_ARG;
+    if (jobv == 'V' && (!dV || bad_block(n, n, ldv, strideV))) return QR_E_ARG;
+    if (batch == 0) return 0;
+    const size_t sa = (size_t) strideA, sj = (size_t) stridejpvt, st = (size_t) stridetau;
+    double* U = jobu == 'U' ? dU : NULL;
+    double* V = jobv == 'V' ? dV : NULL;
+    CHECK(qrd_b_geqp3(p->stream, dA, m, n, lda, sa, djpvt, sj, dtau, st, NULL, 0, 0, 0, 0.0, 0, NULL, NULL, batch));
+    CHECK(qrd_b_jsvd(p->stream, dA, m, n, lda, sa, djpvt, sj, dS, (size_t) strideS, U, ldu, (size_t) strideU, V, ldv, (size_t) strideV, drank,
+                     dsweeps, dinfo, QR_JSVD_MAX_SWEEPS, batch));
+    if (!U) return 0;
+    return qrd_b_ormqr(p->stream, 0, dA, m, n, lda, sa, dtau, st, U, n, ldu, (size_t) strideU, batch);
+}
+
+int qr_svd_batched(const double* A, int m, int n, int batch, double* S, double* U, double* V, int* rank)
+{
+    if (!A || !S || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || batch < 0) return QR_E_ARG;
+    if (batch == 0) return 0;
+    const size_t mn = (size_t) m * n, nn = (size_t) n * n, nb = (size_t) batch;
+    qr_plan* p = NULL;
+    CHECK(qr_plan_create(&p, m, n, 0, 0));
+    double* d = NULL;
+    int* di = NULL;
+    int *dj = NULL, *drank = NULL, *dinfo = NULL;
+    double *dA = NULL, *dtau = NULL, *dS = NULL, *dU = NULL, *dV = NULL;
+    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (mn + 2 * (size_t) n + (U ? mn : 0) + (V ? nn : 0)));
+    if (!rc) {
+        dA = d; dtau = dA + nb * mn; dS = dtau + nb * (size_t) n;
+        double* next = dS + nb * (size_t) n;
+        if (U) { dU = next; next += nb * mn; }
+        if (V) dV = next;
+    }
+    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * ((size_t) n + 2));
+    if (!rc) { dj = di; drank = di + nb * (size_t) n; dinfo = drank + nb; }
+    int* info = (int*) malloc(sizeof(int) * nb);
+    if (!rc && !info) rc = QR_E_ALLOC;
+    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
+    if (!rc)
+        rc = qr_gesvd_batched_dev(p, U ? 'U' : 'N', V ? 'V' : 'N', dA, m, n, m, (long long) mn, dj, n, dtau, n, dS, n, dU, m, (long long) mn, dV, n,
+                                  (long long) nn, drank, NULL, dinfo, batch);
+    if (!rc) rc = qrd_d2h(p->stream, S, dS, sizeof(double) * nb * (size_t) n);
+    if (!rc && U) rc = qrd_d2h(p->stream, U, dU, sizeof(double) * nb * mn);
+    if (!rc && V) rc = qrd_d2h(p->stream, V, dV, sizeof(double) * nb * nn);
+    if (!rc && rank) rc = qrd_d2h(p->stream, rank, drank, sizeof(int) * nb);
+    if (!rc) rc = qrd_d2h(p->stream, info, dinfo, sizeof(int) * nb);
+    const int rs = qrd_stream_sync(p->stream);
+    if (!rc) rc = rs;
+    if (!rc)
+        for (size_t q = 0; q < nb; ++q)
+            if (info[q]) rc = QR_E_NOCONV;
+    free(info);
     if (di) qrd_free(di);
     if (d) qrd_free(d);
     qr_plan_destroy(p);

@@ -291,6 +291,15 @@ int qrd_b_geqp3(void* stream, double* A, int m, int n, int lda, size_t strideA, 
 int qrd_b_rank(void* stream, const double* A, int n, int lda, size_t strideA, double rcond, int* rank, int batch);
 int qrd_b_solve_piv(void* stream, const double* A, int m, int n, int lda, size_t strideA, const int* jpvt, size_t stridej, double* B, int nrhs,
                     int ldb, size_t strideB, double rcond, int minnorm, double* resid, int* rank, int batch);
+/* the batched SVD's kernel (qr_batched_svd.hip; mi355x_qr.h section 8c): from the factors and jpvt of qrd_b_geqp3, per matrix the rank cut
+ * r (the leading run of |R(i,i)| > sqrt(n) eps |R(0,0)|), one-sided Jacobi on (R with rows r.. dropped)^T in LDS, S (n values, descending,
+ * exact zeros past r), V (n x n, NULL: not wanted) = P times the normalised columns, completed to an orthonormal basis where r < n, and
+ * U (m x n, NULL: not wanted) <- [W; 0], the accumulated rotations in sorted column order, which qrd_b_ormqr (trans_t = 0) turns into the
+ * left singular vectors.  rank and sweeps may be NULL; info[q] = 0, or 1 where max_sweeps sweeps did not converge.  One launch: a wave
+ * per matrix for n <= 32, a workgroup above.  A is read only. */
+int qrd_b_jsvd(void* stream, const double* A, int m, int n, int lda, size_t strideA, const int* jpvt, size_t stridej, double* S,
+               size_t strideS, double* U, int ldu, size_t strideU, double* V, int ldv, size_t strideV, int* rank, int* sweeps, int* info,
+               int max_sweeps, int batch);
 
 #define QRD_LEAFW 32
 

@@ -38,6 +38,10 @@
  * m x rank and rank x n factors; default n) and one right-hand side each go through one qr_gelsy_batched_dev call: the time, the
  * smallest and largest rank found, and the worst ||A^T (A x - b)|| / (||A||_F^2 ||x|| + ||A||_F ||b||) over the batch (zero at a
  * least-squares solution; formed on the host).
+ *
+ * `./qr_device m n --batched count --svd` does nothing else either: `count` seeded m x n matrices go through one qr_gesvd_batched_dev call
+ * with U and V (batch resident in HBM): the time, the largest sweep count, and the worst ||A - U S V^T||_F / ||A||_F over the batch
+ * (formed on the host).
  */
 #include <math.h>
 #include <stdio.h>
@@ -552,9 +556,79 @@ static int batched_pivot_main(int m, int n, int count, int rank)
     return 0;
 }
 
+/* count matrices of m x n through one batched SVD call */
+static int batched_svd_main(int m, int n, int count)
+{
+    if (n < 1 || n > QR_BATCHED_MAX_N || m < n || count < 1) {
+        fprintf(stderr, "--batched count --svd needs count >= 1 and 1 <= n <= %d, n <= m\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d matrices of %dx%d\n", count, m, n);
+    const size_t mn = (size_t) m * n, nn = (size_t) n * n, cnt = mn * count;
+    double *A = malloc(sizeof(double) * cnt), *U = malloc(sizeof(double) * cnt), *V = malloc(sizeof(double) * nn * count);
+    double* S = malloc(sizeof(double) * (size_t) n * count);
+    int *sw = malloc(sizeof(int) * (size_t) count), *info = malloc(sizeof(int) * (size_t) count);
+    if (!A || !U || !V || !S || !sw || !info) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    qr_plan* p = NULL;
+    double *dA = NULL, *dtau = NULL, *dS = NULL, *dU = NULL, *dV = NULL;
+    int *dj = NULL, *dsw = NULL, *dinfo = NULL;
+    if (qr_plan_create(&p, m, n, 0, 0) || qr_device_malloc((void**) &dA, sizeof(double) * cnt) || qr_device_malloc((void**) &dU, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dV, sizeof(double) * nn * count) || qr_device_malloc((void**) &dtau, sizeof(double) * (size_t) n * count) ||
+        qr_device_malloc((void**) &dS, sizeof(double) * (size_t) n * count) || qr_device_malloc((void**) &dj, sizeof(int) * (size_t) n * count) ||
+        qr_device_malloc((void**) &dsw, sizeof(int) * (size_t) count) || qr_device_malloc((void**) &dinfo, sizeof(int) * (size_t) count)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dA, A, sizeof(double) * cnt)) { fprintf(stderr, "copy failed\n"); return 1; }
+        const double t0 = now();
+        int rc = qr_gesvd_batched_dev(p, 'U', 'V', dA, m, n, m, (long long) mn, dj, n, dtau, n, dS, n, dU, m, (long long) mn, dV, n, (long long) nn,
+                                      NULL, dsw, dinfo, count);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc) {
+            fprintf(stderr, "qr_gesvd_batched_dev failed: %s%s\n", qr_strerror(rc), rc == QR_E_ARG ? " (the matrix does not fit the LDS: see qr_batched_max_rows)" : "");
+            return 1;
+        }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(U, dU, sizeof(double) * cnt) || qr_copy_to_host(V, dV, sizeof(double) * nn * count) ||
+        qr_copy_to_host(S, dS, sizeof(double) * (size_t) n * count) || qr_copy_to_host(sw, dsw, sizeof(int) * (size_t) count) ||
+        qr_copy_to_host(info, dinfo, sizeof(int) * (size_t) count)) {
+        fprintf(stderr, "copy back failed\n");
+        return 1;
+    }
+    int swmax = 0, noconv = 0;
+    double worst = 0.0;
+    for (int q = 0; q < count; q++) {
+        const double *a = A + q * mn, *u = U + q * mn, *v = V + q * nn, *sg = S + (size_t) q * n;
+        if (sw[q] > swmax) swmax = sw[q];
+        noconv += info[q] != 0;
+        double num = 0.0, den = 0.0;
+        for (int j = 0; j < n; j++)
+            for (int i = 0; i < m; i++) {
+                double s = -a[(size_t) j * m + i];
+                for (int k = 0; k < n; k++) s += u[(size_t) k * m + i] * sg[k] * v[(size_t) k * n + j];
+                num += s * s;
+                den += a[(size_t) j * m + i] * a[(size_t) j * m + i];
+            }
+        if (den > 0.0 && sqrt(num / den) > worst) worst = sqrt(num / den);
+    }
+    printf(" MMQR ran the SVD of %d %dx%d matrices in %f s (avg over %d)   [batch resident in HBM, U and V formed]\n", count, m, n, el / TRIALS,
+           TRIALS);
+    printf(" largest sweep count = %d   not converged = %d   worst ||A - U S V^T|| / ||A|| = %.2e\n", swmax, noconv, worst);
+    qr_device_free(dA); qr_device_free(dU); qr_device_free(dV); qr_device_free(dtau); qr_device_free(dS); qr_device_free(dj);
+    qr_device_free(dsw); qr_device_free(dinfo);
+    qr_plan_destroy(p);
+    free(A); free(U); free(V); free(S); free(sw); free(info);
+    return noconv ? 1 : 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank]]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -570,6 +644,8 @@ int main(int argc, char** argv)
                 if (strcmp(argv[k], "--pivot") == 0)
                     return batched_pivot_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]),
                                               k + 1 < argc && argv[k + 1][0] != '-' ? atoi(argv[k + 1]) : atoi(argv[2]));
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--svd") == 0) return batched_svd_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             return batched_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
         }
     for (int i = 3; i < argc; i++)

@@ -729,6 +729,56 @@ int qr_thin_pivoted_batched(const double* A, int m, int n, int batch, double* Q,
 int qr_lstsq_pivoted_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, double rcond, int minnorm,
                              double* X, double* resid, int* rank, int* jpvt);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8c. Batched singular value decomposition of small matrices: A = U diag(S) V^T for every matrix of a batch (m >= n) -- per-sample PCA,
+ * Procrustes / Kabsch alignment, per-element pseudo-inverses, condition numbers, low-rank truncation, what torch.linalg.svd on a batch is
+ * used for.  Sections 8 and 8b's conventions hold unchanged: the layout (base + q * stride, column-major, strides in elements), the shape
+ * limits (n <= QR_BATCHED_MAX_N, m as qr_batched_max_rows describes), the plan that supplies the stream only, no host wait, QR_E_ARG for
+ * bad arguments before anything touches a device, batch == 0 returns 0 after the checks, no atomics, every sum in an order that n alone
+ * fixes, results bitwise repeatable and bitwise independent of `batch` and of a matrix's index.
+ *
+ * Per matrix:
+ *   1. A P = Q R by qr_geqp3_batched_dev's kernel.
+ *   2. The rank cut: r = the length of the leading run of |R(i,i)| > sqrt(n) * DBL_EPSILON * |R(0,0)| (LAPACK dgejsv's threshold for an
+ *      absolute error bound), 0 if R(0,0) == 0.  Rows r..n-1 of R are dropped: the diagonal of a pivoted R bounds every later row, so their
+ *      Frobenius norm is at most n eps |R(0,0)|.  The threshold is fixed; there is no rcond argument.
+ *   3. One-sided Jacobi on G = (R with rows r.. zeroed)^T, n x n in LDS; its columns r..n-1 are exact zeros and are never touched.  The
+ *      pairs come in the round-robin circle ordering of qr_jsvd_round_pairs taken column by column.  For (p, q): a = g_p.g_p, b = g_q.g_q,
+ *      c = g_p.g_q; the pair is skipped if a or b is 0, if |c| <= tol sqrt(a) sqrt(b) with tol = sqrt(n) * DBL_EPSILON, or if it is not live
+ *      by section 7's rule (a > eps^2 b and b > eps^2 a); otherwise the rotation of the smaller angle, zeta = (b - a) / (2 c),
+ *      t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)), is applied to G and, when U is wanted, to W (n x n, starts as I).  The iteration ends
+ *      with the first sweep that rotated nothing (that sweep is counted), at QR_JSVD_MAX_SWEEPS at the latest.
+ *   4. S = the column norms of G, sorted descending and stably; the live columns of V = P times the normalised columns of G.
+ *   5. Where r < n, the n - r columns of V that belong to S = 0 complete the live ones to an orthonormal basis (the trailing columns of the
+ *      Q of a Householder QR of the live block); the live columns are kept as computed.
+ *   6. U = Q [W; 0] by qr_ormqr_batched_dev's kernel: every column of U is a unit vector, and those for S = 0 are Q's columns r..n-1.
+ * Pivoting and the rank cut are what make the rank-deficient members of a batch converge (Jacobi on R itself, or on R^T of an unpivoted
+ * QR, did not).  Three launches whatever `batch` is (geqp3, Jacobi, ormqr), two when U is not wanted.  n <= 32: one wave per matrix, four
+ * matrices per workgroup; above: one workgroup per matrix.
+ *
+ * Out of scope: a single fused launch; wide matrices (m < n: factor the transpose); n > QR_BATCHED_MAX_N; a caller-chosen threshold.
+ * ------------------------------------------------------------------------------------------- */
+
+/* jobu 'U' / 'N' and jobv 'V' / 'N' select the outputs.  dA, djpvt and dtau come back as qr_geqp3_batched_dev leaves them, so
+ * qr_ormqr_batched_dev keeps working on them.  dS: n values per matrix, descending and non-negative, exactly 0.0 beyond the rank cut.
+ * dU: m x n per matrix (jobu 'N': not referenced, may be NULL); dV: n x n per matrix, V and not V^T (jobv 'N': may be NULL); per matrix
+ * A = dU diag(dS) dV^T.  drank (batch ints, may be NULL) = the number of non-zero values; dsweeps (batch ints, may be NULL) = the sweeps
+ * used; dinfo (batch ints, required) = 0, or 1 where QR_JSVD_MAX_SWEEPS was reached -- the call still returns 0 and the other matrices
+ * are valid.  QR_E_ARG, besides what section 8b rejects: an unknown job letter, dS or dinfo NULL, strideS < n, and for an output that is
+ * wanted a NULL pointer, ldu < m, strideU < ldu * n, ldv < n or strideV < ldv * n.  Nothing outside the stated extents is written. */
+int qr_gesvd_batched_dev(qr_plan* plan, char jobu, char jobv,
+                         double* dA, int m, int n, int lda, long long strideA,
+                         int* djpvt, long long stridejpvt, double* dtau, long long stridetau,
+                         double* dS, long long strideS,
+                         double* dU, int ldu, long long strideU,
+                         double* dV, int ldv, long long strideV,
+                         int* drank, int* dsweeps, int* dinfo, int batch);
+
+/* The SVD of a packed batch on host pointers (A untouched; lda = m, stride = m * n): S n values per matrix, U m x n, V n x n (column-major,
+ * packed) and rank (batch ints); U, V and rank may each be NULL.  Creates a plan of its own.  Synchronous.  Returns QR_E_NOCONV if any
+ * matrix reached QR_JSVD_MAX_SWEEPS. */
+int qr_svd_batched(const double* A, int m, int n, int batch, double* S, double* U, double* V, int* rank);
+
 #ifdef __cplusplus
 }
 #endif
