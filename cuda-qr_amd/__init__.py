@@ -172,6 +172,23 @@ _sig("qr_lstsq_pivoted_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C
 _sig("qr_gesvd_batched_dev", C.c_int, _vp, C.c_char, C.c_char, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, C.c_int, _ll,
      _vp, C.c_int, _ll, _vp, _vp, _vp, C.c_int)
 _sig("qr_svd_batched", C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip)
+_sig("qr_tpqrt_batched_max_rows", C.c_int, C.c_int)
+_sig("qr_tphqrt_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, _ll, _vp, C.c_int,
+     _ll, C.c_int, _vp, C.c_int)
+_sig("qr_tpqrt_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, _ll, _vp, C.c_int, _ll,
+     C.c_int, C.c_int)
+_sig("qr_tpmqrt_batched_dev", C.c_int, _vp, C.c_char, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, _ll, _vp, C.c_int, _ll,
+     C.c_int, C.c_int)
+_sig("qr_lsacc_batched_create", C.c_int, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int)
+_sig("qr_lsacc_batched_push_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll)
+_sig("qr_lsacc_batched_pop_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp)
+_sig("qr_lsacc_batched_slide_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp)
+_sig("qr_lsacc_batched_factor_dev", C.c_int, _vp, C.POINTER(_vp), _ip, C.POINTER(_ll), C.POINTER(_vp), _ip, C.POINTER(_ll), C.POINTER(_vp),
+     C.POINTER(_vp))
+_sig("qr_lsacc_batched_solve_dev", C.c_int, _vp, _vp, C.c_int, _ll, _vp, _ll, _vp)
+_sig("qr_lsacc_batched_reset", C.c_int, _vp)
+_sig("qr_lsacc_batched_destroy", C.c_int, _vp)
+_sig("qr_lstsq_rolling_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -580,6 +597,34 @@ def svd_batched(A, compute_uv=True):
     return U.transpose(0, 2, 1), S, V.transpose(0, 2, 1), rank
 
 
+def tpqrt_batched_max_rows(ncols):
+    """the most rows p_add + p_del one batched update takes beside ncols = n + nrhs columns (qr_tpqrt_batched_max_rows; 0: too many
+    columns; no device)"""
+    return lib.qr_tpqrt_batched_max_rows(int(ncols))
+
+
+def lstsq_rolling_batched(A, B, window, step):
+    """least squares over the windows A[q, k step : k step + window] of every series of A (batch, m, n) and B (batch, m, nrhs) through
+    qr_lstsq_rolling_batched: the first window is pushed, every later one is one slide for the whole batch.  Returns (X, resid, info):
+    X (batch, windows, n, nrhs), resid (batch, windows, nrhs), info (batch, windows) with 0, the failing column + 1 or -1 of a slide, or
+    the zero pivot + 1 of a solve.  A non-zero info word does not raise: the other entries are valid."""
+    At = _packed_batch(A, "lstsq_rolling_batched")
+    Bt = _packed_batch(B, "lstsq_rolling_batched")
+    batch, n, m = At.shape
+    if Bt.shape[0] != batch or Bt.shape[2] != m:
+        raise QRError(f"lstsq_rolling_batched: B is {Bt.shape[0]} series of {Bt.shape[2]} rows, A is {batch} of {m}", QR_E_ARG)
+    nrhs = Bt.shape[1]
+    window, step = int(window), int(step)
+    nwin = (m - window) // step + 1 if 1 <= step and n <= window <= m else 1
+    X = np.empty((batch, nwin, nrhs, n))
+    resid = np.empty((batch, nwin, nrhs))
+    info = np.zeros((max(batch, 1), nwin), dtype=np.intc)
+    rc = lib.qr_lstsq_rolling_batched(_p(At), m, n, _p(Bt), nrhs, batch, window, step, _p(X), _p(resid), info.ctypes.data_as(_ip))
+    if rc not in (QR_E_SINGULAR, QR_E_NOTPD):
+        check(rc, "qr_lstsq_rolling_batched")
+    return X.transpose(0, 1, 3, 2), resid, info[:batch].astype(np.int64)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -854,6 +899,26 @@ class Plan:
         check(lib.qr_tphmqrt_dev(self.h, _dptr(dV), p_add, p_del, n, ldv, _dptr(dT), ldt, _dptr(dC1), ldc1, _dptr(dC2), ldc2, nrhs),
               "qr_tphmqrt_dev")
 
+    def tphqrt_batched(self, dR, n, ldr, strideR, dB, p_add, p_del, ldb, strideB, dtau, stridetau, dinfo, batch, dC1=None, ldc1=0, strideC1=0,
+                       dC2=None, ldc2=0, strideC2=0, nrhs=0):
+        """the signed-row update of `batch` triangles: dB_q's first p_add rows are added to dR_q, its last p_del rows removed; dB <- V,
+        dtau <- tau (n per member); [dC1 ; dC2] (nrhs columns) ride along; dinfo (batch device ints): 0 or the failing column + 1, and
+        such a member is left untouched.  Does not wait."""
+        check(lib.qr_tphqrt_batched_dev(self.h, _dptr(dR), n, ldr, strideR, _dptr(dB), p_add, p_del, ldb, strideB, _dptr(dtau), stridetau,
+                                        _dptr(dC1), ldc1, strideC1, _dptr(dC2), ldc2, strideC2, nrhs, _dptr(dinfo), batch),
+              "qr_tphqrt_batched_dev")
+
+    def tpqrt_batched(self, dR, n, ldr, strideR, dB, p, ldb, strideB, dtau, stridetau, batch, dC1=None, ldc1=0, strideC1=0, dC2=None, ldc2=0,
+                      strideC2=0, nrhs=0):
+        """the row-append update of `batch` triangles (tphqrt_batched with p_del = 0; it cannot fail)"""
+        check(lib.qr_tpqrt_batched_dev(self.h, _dptr(dR), n, ldr, strideR, _dptr(dB), p, ldb, strideB, _dptr(dtau), stridetau, _dptr(dC1), ldc1,
+                                       strideC1, _dptr(dC2), ldc2, strideC2, nrhs, batch), "qr_tpqrt_batched_dev")
+
+    def tpmqrt_batched(self, trans, dV, p_add, p_del, n, ldv, strideV, dtau, stridetau, dC1, ldc1, strideC1, dC2, ldc2, strideC2, nrhs, batch):
+        """[C1 ; C2]_q <- the transformation of tphqrt_batched / tpqrt_batched (trans 'T') or, for p_del == 0, its inverse ('N')"""
+        check(lib.qr_tpmqrt_batched_dev(self.h, trans.encode(), _dptr(dV), p_add, p_del, n, ldv, strideV, _dptr(dtau), stridetau, _dptr(dC1),
+                                        ldc1, strideC1, _dptr(dC2), ldc2, strideC2, nrhs, batch), "qr_tpmqrt_batched_dev")
+
     def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
         """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""
         check(lib.qr_geqrf_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, batch), "qr_geqrf_batched_dev")
@@ -1055,6 +1120,70 @@ class LsAccumulator:
 
     def reset(self):
         check(lib.qr_lsacc_reset(self.h), "qr_lsacc_reset")
+
+
+class LsAccumulatorBatched:
+    """qr_lsacc_batched wrapper: one least-squares accumulator per member of a batch (R, Q^T b, the residual sums of squares and the row
+    counts stay on the device); push, pop and slide are one launch for the whole batch.  The plan must stay open for as long as the
+    accumulator is used."""
+
+    def __init__(self, plan, n, nrhs, batch):
+        self.h = None
+        h = _vp()
+        check(lib.qr_lsacc_batched_create(C.byref(h), plan.h, n, nrhs, batch), "qr_lsacc_batched_create")
+        self.h, self.plan, self.n, self.nrhs, self.batch = h, plan, n, nrhs, batch
+
+    def close(self):
+        if self.h and lib is not None and self.plan.h:
+            lib.qr_lsacc_batched_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def push(self, dA, p, lda, strideA, dB, ldb, strideB):
+        """fold p rows [dA_q | dB_q] into every member (inputs untouched)"""
+        check(lib.qr_lsacc_batched_push_dev(self.h, _dptr(dA), p, lda, strideA, _dptr(dB), ldb, strideB), "qr_lsacc_batched_push_dev")
+
+    def pop(self, dA, p, lda, strideA, dB, ldb, strideB, dinfo):
+        """remove p rows that were pushed earlier; dinfo (batch device ints): 0, the failing column + 1, or -1 (fewer than n rows left);
+        a member with a non-zero word keeps its state"""
+        check(lib.qr_lsacc_batched_pop_dev(self.h, _dptr(dA), p, lda, strideA, _dptr(dB), ldb, strideB, _dptr(dinfo)),
+              "qr_lsacc_batched_pop_dev")
+
+    def slide(self, dAnew, pnew, ldan, strideAn, dBnew, ldbn, strideBn, dAold, pold, ldao, strideAo, dBold, ldbo, strideBo, dinfo):
+        """add pnew rows and remove pold rows in one launch; dinfo as pop"""
+        check(lib.qr_lsacc_batched_slide_dev(self.h, _dptr(dAnew), pnew, ldan, strideAn, _dptr(dBnew), ldbn, strideBn, _dptr(dAold), pold, ldao,
+                                             strideAo, _dptr(dBold), ldbo, strideBo, _dptr(dinfo)), "qr_lsacc_batched_slide_dev")
+
+    def factor(self):
+        """(dR, ldr, strideR, dZ, ldz, strideZ, drss, drows): device addresses (ints), leading dimensions and strides of the state"""
+        r, z, s, w = _vp(), _vp(), _vp(), _vp()
+        ldr, ldz, sr, sz = C.c_int(), C.c_int(), _ll(), _ll()
+        check(lib.qr_lsacc_batched_factor_dev(self.h, C.byref(r), C.byref(ldr), C.byref(sr), C.byref(z), C.byref(ldz), C.byref(sz), C.byref(s),
+                                              C.byref(w)), "qr_lsacc_batched_factor_dev")
+        return r.value, ldr.value, sr.value, z.value, ldz.value, sz.value, s.value, w.value
+
+    def factor_host(self):
+        """numpy copies (R (batch, n, n), Z (batch, n, nrhs), rss (batch, nrhs), rows (batch,)) of the state; synchronises the plan"""
+        r, _, _, z, _, _, s, w = self.factor()
+        self.plan.sync()
+        R = np.empty((self.batch, self.n, self.n))
+        Z = np.empty((self.batch, self.nrhs, self.n))
+        rss = np.empty((self.batch, self.nrhs))
+        rows = np.zeros(self.batch, dtype=np.intc)
+        if self.batch:
+            for host, dev in ((R, r), (Z, z), (rss, s), (rows, w)):
+                check(lib.qr_copy_to_host(host.ctypes.data, dev, host.nbytes), "qr_copy_to_host")
+        return R.transpose(0, 2, 1), Z.transpose(0, 2, 1), rss, rows.astype(np.int64)
+
+    def solve(self, dX, ldx, strideX, dinfo, dresid=None, strideresid=0):
+        """dX_q (n x nrhs) <- the least-squares solution of the rows member q holds; dresid (nrhs per member) <- the residual norms;
+        dinfo: 0 or the first zero pivot + 1"""
+        check(lib.qr_lsacc_batched_solve_dev(self.h, _dptr(dX), ldx, strideX, _dptr(dresid), strideresid, _dptr(dinfo)),
+              "qr_lsacc_batched_solve_dev")
+
+    def reset(self):
+        check(lib.qr_lsacc_batched_reset(self.h), "qr_lsacc_batched_reset")
 
 
 class TsqrPlan:

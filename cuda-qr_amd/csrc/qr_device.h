@@ -301,6 +301,39 @@ int qrd_b_jsvd(void* stream, const double* A, int m, int n, int lda, size_t stri
                size_t strideS, double* U, int ldu, size_t strideU, double* V, int ldv, size_t strideV, int* rank, int* sweeps, int* info,
                int max_sweeps, int batch);
 
+/* batched row append / removal (qr_batched_update.hip, called from qr_batched_update.c only -- as above, the stub device layer does not
+ * have them; mi355x_qr.h section 8d).  Per member the n x n triangle R (and Z, n x nrhs, riding along) stacked on a block of p rows of
+ * n + nrhs columns, of which rows [0, p_add) count +1 and rows [p_add, p) count -1.  The block is described by two pairs of buffers: entry
+ * (i, c) of its first n columns is A0[q sA0 + c lda0 + i] for i < p_add and A1[q sA1 + c lda1 + (i - p_add)] otherwise, and C0 / C1 hold
+ * the last nrhs columns in the same way (a pair that covers no row is not referenced).
+ *   acc == 0  the primitive: V and the transformed right-hand-side rows go back over the block, tau (n per member, stau apart) is written
+ *   acc != 0  the accumulator: the block is read only; rss (nrhs per member, packed) <- max(0, rss + |E_add|^2 - |E_del|^2) and rows (one
+ *             int per member) += p_add - p_del; a member with p_del > 0 and rows + p_add - p_del < n gets info -1 before any arithmetic
+ * info (one int per member; may be NULL when p_add == p): 0, the failing column + 1, or -1; on a non-zero value nothing else is written
+ * for that member.  One launch: a wave per member for n + nrhs <= 32 and p <= 64 (qrd_bu_wave_route), else a workgroup per member.
+ * qrd_bu_max_rows: QRD_BU_MAXROWS for 1 .. 32 columns (one block row per thread), QRD_BU_MAXROWS_WIDE for 33 .. 64 (64 columns at a
+ * leading dimension of 226 beside the 64 x 65 triangle are 149 568 of the 163 840 bytes; the next leading dimension, 258, does not fit),
+ * 0 otherwise.
+ * qrd_bu_apply: [C1 ; C2] <- the stored transformation (trans_t = 1) or, for p_add == p only, its inverse (0), any nrhs >= 1, one launch.
+ * qrd_bu_solve_prep: X_q <- Z_q and resid (may be NULL) <- sqrt(rss), ahead of qrd_b_trsm.  batch <= 0: nothing is launched.  -7: shape not taken */
+#define QRD_BU_MAXROWS 256
+#define QRD_BU_MAXROWS_WIDE 226
+typedef struct qrd_bu_args {
+    double *R, *Z, *tau, *rss;
+    int *rows, *info;
+    double *A0, *A1, *C0, *C1;
+    size_t sR, sZ, stau, sA0, sA1, sC0, sC1;
+    int ldr, ldz, lda0, lda1, ldc0, ldc1;
+    int n, nrhs, p, p_add, batch, acc;
+} qrd_bu_args;
+int qrd_bu_max_rows(int ncols);
+int qrd_bu_wave_route(int ncols, int p);
+int qrd_bu_update(void* stream, const qrd_bu_args* a);
+int qrd_bu_apply(void* stream, int trans_t, const double* V, int p, int p_add, int n, int ldv, size_t strideV, const double* tau,
+                 size_t stridetau, double* C1, int ldc1, size_t strideC1, double* C2, int ldc2, size_t strideC2, int nrhs, int batch);
+int qrd_bu_solve_prep(void* stream, const double* Z, int n, int nrhs, double* X, int ldx, size_t strideX, const double* rss, double* resid,
+                      size_t strideresid, int batch);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

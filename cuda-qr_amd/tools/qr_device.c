@@ -42,6 +42,11 @@
  * `./qr_device m n --batched count --svd` does nothing else either: `count` seeded m x n matrices go through one qr_gesvd_batched_dev call
  * with U and V (batch resident in HBM): the time, the largest sweep count, and the worst ||A - U S V^T||_F / ||A||_F over the batch
  * (formed on the host).
+ *
+ * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
+ * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
+ * qr_lsacc_batched_slide_dev for the whole batch -- beside one qr_gels_batched_dev per window on copies of the windows: both wall times
+ * and the largest solution error ||x_acc - x||_2 / ||x||_2 over every window and series.
  */
 #include <math.h>
 #include <stdio.h>
@@ -466,6 +471,87 @@ static int batched_main(int m, int n, int count)
     return 0;
 }
 
+/* count series of m rows through one batched accumulator, window by window, beside one batched solve per window */
+static int batched_slide_main(int m, int n, int count, int window, int step)
+{
+    const int nrhs = 1;
+    if (n < 1 || n + nrhs > QR_BATCHED_MAX_N || count < 1 || window < n || window > m || step < 1 || step > window ||
+        2 * step > qr_tpqrt_batched_max_rows(n + nrhs) || window > qr_batched_max_rows(n + nrhs)) {
+        fprintf(stderr, "--batched count --slide window step needs count >= 1, 1 <= n < %d, n <= window <= min(m, %d), 1 <= step <= window and "
+                        "2 step <= %d\n", QR_BATCHED_MAX_N, qr_batched_max_rows(n + nrhs), qr_tpqrt_batched_max_rows(n + nrhs));
+        return 1;
+    }
+    const int nwin = (m - window) / step + 1;
+    printf("Exact problem size: %d series of %dx%d, %d windows of %d rows, step %d\n", count, m, n, nwin, window, step);
+    const size_t mn = (size_t) m * n, wn = (size_t) window * n, nb = (size_t) count;
+    double *A = malloc(sizeof(double) * nb * mn), *B = malloc(sizeof(double) * nb * m), *X = malloc(sizeof(double) * nb * n),
+           *C = malloc(sizeof(double) * nb * window);
+    int* info = malloc(sizeof(int) * nb);
+    if (!A || !B || !X || !C || !info) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < nb * mn; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    for (size_t i = 0; i < nb * m; i++) B[i] = (double) rand() / RAND_MAX - 0.5;
+    qr_plan* p = NULL;
+    qr_lsacc_batched* acc = NULL;
+    double *dA = NULL, *dB = NULL, *dW = NULL, *dC = NULL, *dtau = NULL, *dX = NULL;
+    int* dinfo = NULL;
+    if (qr_plan_create(&p, window, n, 0, 0) || qr_lsacc_batched_create(&acc, p, n, nrhs, count) ||
+        qr_device_malloc((void**) &dA, sizeof(double) * nb * mn) || qr_device_malloc((void**) &dB, sizeof(double) * nb * m) ||
+        qr_device_malloc((void**) &dW, sizeof(double) * nb * wn) || qr_device_malloc((void**) &dC, sizeof(double) * nb * window) ||
+        qr_device_malloc((void**) &dtau, sizeof(double) * nb * n) || qr_device_malloc((void**) &dX, sizeof(double) * nb * n) ||
+        qr_device_malloc((void**) &dinfo, sizeof(int) * nb) || qr_copy_to_device(dA, A, sizeof(double) * nb * mn) ||
+        qr_copy_to_device(dB, B, sizeof(double) * nb * m)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el_acc = 0.0, el_ref = 0.0, worst = 0.0;
+    int bad = 0;
+    for (int k = 0; k < nwin; k++) {
+        const size_t o = (size_t) (k - 1) * step, e = o + window;
+        double t0 = now();
+        int rc = k == 0 ? qr_lsacc_batched_push_dev(acc, dA, window, m, (long long) mn, dB, m, m)
+                        : qr_lsacc_batched_slide_dev(acc, dA + e, step, m, (long long) mn, dB + e, m, m, dA + o, step, m, (long long) mn, dB + o,
+                                                     m, m, dinfo);
+        if (!rc && k > 0) rc = qr_copy_to_host(info, dinfo, sizeof(int) * nb);         /* (waits: the slide's info words) */
+        for (size_t q = 0; !rc && k > 0 && q < nb; q++) bad += info[q] != 0;
+        if (!rc) rc = qr_lsacc_batched_solve_dev(acc, dX, n, n, NULL, 0, dinfo);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc) { fprintf(stderr, "the batched accumulator failed at window %d: %s\n", k, qr_strerror(rc)); return 1; }
+        el_acc += now() - t0;
+        if (qr_copy_to_host(X, dX, sizeof(double) * nb * n)) { fprintf(stderr, "copy failed\n"); return 1; }
+        /* the same window from scratch: copies of its rows, one fused qr_gels_batched_dev */
+        for (size_t q = 0; q < nb; q++) {
+            for (int j = 0; j < n; j++)
+                if (qr_copy_to_device(dW + q * wn + (size_t) j * window, A + q * mn + (size_t) j * m + (size_t) k * step, sizeof(double) * window)) return 1;
+            if (qr_copy_to_device(dC + q * window, B + q * m + (size_t) k * step, sizeof(double) * window)) return 1;
+        }
+        t0 = now();
+        rc = qr_gels_batched_dev(p, dW, window, n, window, (long long) wn, dtau, n, dC, nrhs, window, window, dinfo, count);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc) { fprintf(stderr, "qr_gels_batched_dev failed: %s\n", qr_strerror(rc)); return 1; }
+        el_ref += now() - t0;
+        if (qr_copy_to_host(C, dC, sizeof(double) * nb * window)) { fprintf(stderr, "copy failed\n"); return 1; }
+        for (size_t q = 0; q < nb; q++) {
+            double num = 0.0, den = 0.0;
+            for (int i = 0; i < n; i++) {
+                const double x = C[q * window + i], d = X[q * n + i] - x;
+                num += d * d;
+                den += x * x;
+            }
+            if (sqrt(num / den) > worst) worst = sqrt(num / den);
+        }
+    }
+    printf(" MMQR slid %d series of n=%d over %d windows in %f s (one launch per slide, the info words read back each time)\n", count, n, nwin,
+           el_acc);
+    printf(" one qr_gels_batched_dev per window instead: %f s\n", el_ref);
+    printf(" largest ||x_acc - x|| / ||x|| over every window and series = %.2e   (%d slides refused)\n", worst, bad);
+    qr_lsacc_batched_destroy(acc);
+    qr_device_free(dA); qr_device_free(dB); qr_device_free(dW); qr_device_free(dC); qr_device_free(dtau); qr_device_free(dX); qr_device_free(dinfo);
+    qr_plan_destroy(p);
+    free(A); free(B); free(X); free(C); free(info);
+    return 0;
+}
+
 /* count matrices of m x n and of rank `rank` through one pivoted least-squares call */
 static int batched_pivot_main(int m, int n, int count, int rank)
 {
@@ -628,13 +714,16 @@ static int batched_svd_main(int m, int n, int count)
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--slide") == 0) {
             if (i + 2 >= argc) { fprintf(stderr, "--slide needs window and step\n"); return 1; }
+            for (int k = 3; k + 1 < argc; k++)          /* with --batched count: the batched accumulator */
+                if (strcmp(argv[k], "--batched") == 0)
+                    return batched_slide_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[k + 1]), atoi(argv[i + 1]), atoi(argv[i + 2]));
             return slide_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), atoi(argv[i + 2]));
         }
     for (int i = 3; i < argc; i++)

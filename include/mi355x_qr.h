@@ -779,6 +779,107 @@ int qr_gesvd_batched_dev(qr_plan* plan, char jobu, char jobv,
  * matrix reached QR_JSVD_MAX_SWEEPS. */
 int qr_svd_batched(const double* A, int m, int n, int batch, double* S, double* U, double* V, int* rank);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8d. Batched row append and removal, and sliding-window least squares: sections 6 and 6b for every member of a batch in one launch --
+ * recursive least squares per channel, rolling regressions over thousands of series, sliding-window calibration.  Per member the n x n
+ * triangle R is stacked on a block of p_add + p_del rows, of which the first p_add are added and the last p_del removed:
+ * R'^T R' = R^T R + B^T S B, S = diag(+1 .. +1, -1 .. -1).  Section 8's conventions hold unchanged: the layout (member q at base +
+ * q * stride, column-major, strides in elements, packed strides legal, a stride smaller than the block it steps over is QR_E_ARG), the
+ * plan that supplies the stream only, no host wait, QR_E_ARG for bad arguments before anything touches a device, batch == 0 returns 0
+ * after the checks and launches nothing, no atomics, every sum in an order that (n, nrhs, p_add, p_del) alone fix, results bitwise
+ * repeatable and bitwise independent of `batch` and of a member's index.
+ *
+ * Per column the arithmetic is section 6b's: with sa / sd the sums of squares of the added / removed rows of column j,
+ * h = hypot(R(j,j), sqrt(sa)), nd = sqrt(sd), d = (h - nd)(h + nd), beta = -sign(R(j,j)) sqrt(d), tau = (beta - R(j,j)) / beta,
+ * v = b / (R(j,j) - beta); a block column that is exactly zero gives tau = 0 and leaves everything untouched; d <= 0 or d not finite is
+ * the failure.  The update is unblocked (one reflector at a time, like section 8's factorisation): these calls carry tau, n per member,
+ * and no block T.  The strict lower triangle of R is neither read nor written.  Stability is section 6b's.
+ *
+ * Shapes: 1 <= n, nrhs >= 0, n + nrhs <= QR_BATCHED_MAX_N; p_add >= 0, p_del >= 0, 1 <= p_add + p_del <=
+ * qr_tpqrt_batched_max_rows(n + nrhs).  The right-hand sides always ride along as extra columns of the same launch.  One wave per member
+ * (four members per workgroup) for n + nrhs <= 32 and p_add + p_del <= 64; otherwise one workgroup per member with both images in LDS.
+ *
+ * Failure is per member: a member whose removal fails gets its info word and is otherwise not written -- its R, block, tau and
+ * right-hand sides are bitwise what they were; the other members are unaffected and the call returns 0.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The rows p_add + p_del one call of this section takes beside ncols = n + nrhs columns: 256 for 1 <= ncols <= 32 (one block row per
+ * thread of the workgroup), 226 for 33 <= ncols <= 64 (64 columns of the block at a leading dimension of 226 = 2 mod 32 beside the
+ * 64 x 65 image of the triangle are 149 568 of the 163 840 bytes of LDS; the next leading dimension, 258, does not fit), 0 otherwise.
+ * No device is touched. */
+int qr_tpqrt_batched_max_rows(int ncols);
+
+/* [R ; B] -> [R' ; 0] under S for every member: R' over dR's upper triangle (n x n, ldr >= n), V over dB ((p_add + p_del) x n, ldb >=
+ * p_add + p_del; reflector j is [e_j ; V(:, j)]), tau (n per member) to dtau.  nrhs > 0: [C1 ; C2] (dC1: n x nrhs, ldc1 >= n; dC2:
+ * (p_add + p_del) x nrhs) goes through the same transformation, what qr_tphmqrt_dev computes; nrhs == 0: dC1 and dC2 are not referenced.
+ * dinfo (batch device ints): 0, or the failing column + 1; such a member's dR, dB, dtau, dC1 and dC2 are bitwise what they were. */
+int qr_tphqrt_batched_dev(qr_plan* plan, double* dR, int n, int ldr, long long strideR,
+                          double* dB, int p_add, int p_del, int ldb, long long strideB,
+                          double* dtau, long long stridetau,
+                          double* dC1, int ldc1, long long strideC1,
+                          double* dC2, int ldc2, long long strideC2, int nrhs,
+                          int* dinfo, int batch);
+
+/* The p_del == 0 case (LAPACK dtpqrt with L = 0, unblocked, per member): the same kernels, bitwise the same result. */
+int qr_tpqrt_batched_dev(qr_plan* plan, double* dR, int n, int ldr, long long strideR,
+                         double* dB, int p, int ldb, long long strideB,
+                         double* dtau, long long stridetau,
+                         double* dC1, int ldc1, long long strideC1,
+                         double* dC2, int ldc2, long long strideC2, int nrhs, int batch);
+
+/* Applies the stored reflectors to later right-hand sides [C1 ; C2] (any nrhs >= 1; p_add + p_del <= qr_tpqrt_batched_max_rows(n)):
+ * trans 'T' is the transformation that took [R ; B] to [R' ; 0], for any signs; trans 'N' is its inverse and exists for p_del == 0
+ * only (QR_E_ARG otherwise).  One launch. */
+int qr_tpmqrt_batched_dev(qr_plan* plan, char trans, const double* dV, int p_add, int p_del, int n, int ldv, long long strideV,
+                          const double* dtau, long long stridetau,
+                          double* dC1, int ldc1, long long strideC1, double* dC2, int ldc2, long long strideC2,
+                          int nrhs, int batch);
+
+/* The least-squares accumulator of sections 6 and 6b for a batch: per member R (n x n), Z (n x nrhs), one sum of squares per right-hand
+ * side and a row count, all on the device and all zero at the start; nrhs >= 1, n + nrhs <= QR_BATCHED_MAX_N.  The plan must outlive it.
+ *   push_dev    folds p >= 1 rows [dA | dB] (dA: p x n, lda >= p; dB: p x nrhs) into every member, in row blocks of at most
+ *               qr_tpqrt_batched_max_rows(n + nrhs) rows, one launch each (a push cannot fail, so blocks are committed one by one)
+ *   pop_dev     removes p rows that were pushed earlier;  slide_dev adds pnew rows and removes pold rows in one pass, reading the two
+ *               pairs of buffers directly.  Both are ONE launch and require p (pnew + pold) <= qr_tpqrt_batched_max_rows(n + nrhs) --
+ *               QR_E_ARG above it: the caller feeds blocks.  dinfo (batch device ints): 0; the failing column + 1; or -1 where the
+ *               member would be left with fewer than n rows (decided on the device from its row count, before any arithmetic).  On any
+ *               non-zero value that member's R, Z, sums and row count are bitwise what they were.
+ *   The inputs of all three are untouched.  The sums become max(0, rss + |E_add|^2 - |E_del|^2), E = what the transformation leaves in
+ *   the block rows of the right-hand sides.
+ *   factor_dev  the device addresses of R, Z (both at a leading dimension of n, packed), the sums (nrhs per member) and the row counts
+ *               (any argument may be NULL); valid until destroy, changed by every push / pop / slide
+ *   solve_dev   dX (n x nrhs per member, ldx >= n) = R^-1 Z; dresid (nrhs per member, strideresid >= nrhs; may be NULL) = the square
+ *               roots of the sums; dinfo: 0, or i + 1 for the smallest i with R(i,i) == 0 (a member that holds fewer than n rows); such
+ *               a member's dX holds Z.  Two launches.  The state is untouched.
+ *   reset       back to the empty state (stream-ordered);  destroy waits for the plan's stream, then frees.
+ * Every call returns 0 without waiting (destroy excepted). */
+typedef struct qr_lsacc_batched qr_lsacc_batched;
+int qr_lsacc_batched_create(qr_lsacc_batched** acc, qr_plan* plan, int n, int nrhs, int batch);
+int qr_lsacc_batched_push_dev(qr_lsacc_batched* acc, const double* dA, int p, int lda, long long strideA,
+                              const double* dB, int ldb, long long strideB);
+int qr_lsacc_batched_pop_dev(qr_lsacc_batched* acc, const double* dA, int p, int lda, long long strideA,
+                             const double* dB, int ldb, long long strideB, int* dinfo);
+int qr_lsacc_batched_slide_dev(qr_lsacc_batched* acc, const double* dAnew, int pnew, int ldan, long long strideAn,
+                               const double* dBnew, int ldbn, long long strideBn,
+                               const double* dAold, int pold, int ldao, long long strideAo,
+                               const double* dBold, int ldbo, long long strideBo, int* dinfo);
+int qr_lsacc_batched_factor_dev(qr_lsacc_batched* acc, const double** dR, int* ldr, long long* strideR,
+                                const double** dZ, int* ldz, long long* strideZ, const double** drss, const int** drows);
+int qr_lsacc_batched_solve_dev(qr_lsacc_batched* acc, double* dX, int ldx, long long strideX,
+                               double* dresid, long long strideresid, int* dinfo);
+int qr_lsacc_batched_reset(qr_lsacc_batched* acc);
+int qr_lsacc_batched_destroy(qr_lsacc_batched* acc);
+
+/* Least squares over a moving window for a packed batch of series on host pointers (A: m x n per member, lda = m; B: m x nrhs per
+ * member; both untouched).  Window k is rows [k step, k step + window), k = 0 .. (m - window) / step.  X: one n x nrhs solution (ld n)
+ * per window per member, member-major (member q's windows one after the other); resid (nrhs per window per member, may be NULL); info:
+ * one int per window per member in the same order.  The first window is a push, every later one ONE slide for the whole batch.
+ * QR_E_ARG as qr_lstsq_rolling, and for n + nrhs > QR_BATCHED_MAX_N or 2 * step > qr_tpqrt_batched_max_rows(n + nrhs).  Returns
+ * QR_E_NOTPD if some slide's info word is non-zero (that member keeps its previous state), else QR_E_SINGULAR if some solve's is; the
+ * other entries stay valid.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_rolling_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, int window, int step,
+                             double* X, double* resid, int* info);
+
 #ifdef __cplusplus
 }
 #endif
