@@ -189,6 +189,12 @@ _sig("qr_lsacc_batched_solve_dev", C.c_int, _vp, _vp, C.c_int, _ll, _vp, _ll, _v
 _sig("qr_lsacc_batched_reset", C.c_int, _vp)
 _sig("qr_lsacc_batched_destroy", C.c_int, _vp)
 _sig("qr_lstsq_rolling_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip)
+_sig("qr_minnorm_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int)
+_sig("qr_gels_t_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int)
+_sig("qr_transpose_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, C.c_int)
+_sig("qr_gels_wide_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, _vp,
+     C.c_int)
+_sig("qr_lstsq_minnorm_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -625,6 +631,25 @@ def lstsq_rolling_batched(A, B, window, step):
     return X.transpose(0, 1, 3, 2), resid, info[:batch].astype(np.int64)
 
 
+def lstsq_minnorm_batched(A, B):
+    """the minimum-norm solution of A_q X_q = B_q for every member of A (batch, m, n), m <= n, and B (batch, m, nrhs) through
+    qr_lstsq_minnorm_batched: returns (X, info) with X (batch, n, nrhs) and info[q] = 0, or i + 1 for the smallest i with
+    R_q(i,i) == 0 exactly (a zero row of A_q; X[q] then holds no solution, the other members are solved).  A singular member does not
+    raise."""
+    At = _packed_batch(A, "lstsq_minnorm_batched")
+    Bt = _packed_batch(B, "lstsq_minnorm_batched")
+    batch, n, m = At.shape
+    if Bt.shape[0] != batch or Bt.shape[2] != m:
+        raise QRError(f"lstsq_minnorm_batched: B is {Bt.shape[0]} matrices of {Bt.shape[2]} rows, A is {batch} of {m}", QR_E_ARG)
+    nrhs = Bt.shape[1]
+    X = np.empty((batch, nrhs, n))
+    info = np.zeros(max(batch, 1), dtype=np.intc)
+    rc = lib.qr_lstsq_minnorm_batched(_p(At), m, n, _p(Bt), nrhs, batch, _p(X), info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_minnorm_batched")
+    return X.transpose(0, 2, 1), info[:batch].astype(np.int64)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -918,6 +943,28 @@ class Plan:
         """[C1 ; C2]_q <- the transformation of tphqrt_batched / tpqrt_batched (trans 'T') or, for p_del == 0, its inverse ('N')"""
         check(lib.qr_tpmqrt_batched_dev(self.h, trans.encode(), _dptr(dV), p_add, p_del, n, ldv, strideV, _dptr(dtau), stridetau, _dptr(dC1),
                                         ldc1, strideC1, _dptr(dC2), ldc2, strideC2, nrhs, batch), "qr_tpmqrt_batched_dev")
+
+    def minnorm_batched(self, dA, m, n, lda, strideA, dtau, stridetau, dB, nrhs, ldb, strideB, dinfo, batch):
+        """dB_q (m x nrhs; rows 0..n-1 = B_q on entry) <- the minimum-norm X_q of A_q^T X = B from the factors of geqrf_batched / geqp3_batched;
+        dinfo (batch device int32): 0, or i + 1 for the smallest i with R(i,i) == 0 (that member's dB is untouched)"""
+        check(lib.qr_minnorm_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, _dptr(dB), nrhs, ldb, strideB,
+                                         _dptr(dinfo), batch), "qr_minnorm_batched_dev")
+
+    def gels_t_batched(self, dA, m, n, lda, strideA, dtau, stridetau, dB, nrhs, ldb, strideB, dinfo, batch):
+        """dgels 'T' (m >= n) of `batch` small matrices: dA factored in place, dB and dinfo as minnorm_batched"""
+        check(lib.qr_gels_t_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, _dptr(dB), nrhs, ldb, strideB,
+                                        _dptr(dinfo), batch), "qr_gels_t_batched_dev")
+
+    def transpose_batched(self, dS, rows, cols, lds, strideS, dD, ldd, strideD, batch):
+        """dD_q (cols x rows) <- dS_q^T (rows x cols), out of place, rows and cols <= 512"""
+        check(lib.qr_transpose_batched_dev(self.h, _dptr(dS), rows, cols, lds, strideS, _dptr(dD), ldd, strideD, batch),
+              "qr_transpose_batched_dev")
+
+    def gels_wide_batched(self, dA, m, n, lda, strideA, dF, ldf, strideF, dtau, stridetau, dB, nrhs, ldb, strideB, dinfo, batch):
+        """dgels 'N' (m <= n) of `batch` small wide matrices: dA untouched, dF (n x m) and dtau (m) <- the factors of A_q^T, dB_q (n x nrhs;
+        rows 0..m-1 = B_q on entry) <- the minimum-norm X_q; dinfo as minnorm_batched"""
+        check(lib.qr_gels_wide_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dF), ldf, strideF, _dptr(dtau), stridetau, _dptr(dB),
+                                           nrhs, ldb, strideB, _dptr(dinfo), batch), "qr_gels_wide_batched_dev")
 
     def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
         """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""

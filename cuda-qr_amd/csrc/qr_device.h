@@ -334,6 +334,21 @@ int qrd_bu_apply(void* stream, int trans_t, const double* V, int p, int p_add, i
 int qrd_bu_solve_prep(void* stream, const double* Z, int n, int nrhs, double* X, int ldx, size_t strideX, const double* rss, double* resid,
                       size_t strideresid, int batch);
 
+/* batched minimum-norm solves (qr_batched_minnorm.hip, called from qr_batched_minnorm.c only -- as above, the stub device layer does not
+ * have them; mi355x_qr.h section 8e).  (m, n) is the shape of the tall matrix F that is factored, m >= n.
+ * qrd_bm_fused: factor F and solve F^T X = B for minimum norm in one launch; n + nrhs columns are held (qrd_b_fits(m, n + nrhs)), the
+ * route is qrd_b_wave_route(m, n + nrhs).  tr == 0: F is A (lda >= m); tr != 0: F is the transpose of A (n x m, lda >= n), read
+ * through the transposed index map.  The factors go to F (ldf >= m; A itself for the in-place call) in qrd_b_geqrf's layout, bitwise
+ * qrd_b_geqrf's on the same route.  B (m x nrhs, ldb >= m): rows 0..n-1 on entry, X on return.  info[q] = 0 or the smallest i + 1 with
+ * R(i,i) == 0; such a member's B is not written.
+ * qrd_bm_apply: the solve alone from existing factors, any nrhs >= 1, one launch.  qrd_bm_transpose: D_q (cols x rows) = S_q^T, rows and
+ * cols <= QRD_B_MAX_ROWS.  batch <= 0: nothing is launched.  -7: shape not taken */
+int qrd_bm_fused(void* stream, int tr, const double* A, int m, int n, int lda, size_t strideA, double* F, int ldf, size_t strideF, double* tau,
+                 size_t stridetau, double* B, int nrhs, int ldb, size_t strideB, int* info, int batch);
+int qrd_bm_apply(void* stream, const double* A, int m, int n, int lda, size_t strideA, const double* tau, size_t stridetau, double* B, int nrhs,
+                 int ldb, size_t strideB, int* info, int batch);
+int qrd_bm_transpose(void* stream, const double* S, int rows, int cols, int lds, size_t strideS, double* D, int ldd, size_t strideD, int batch);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

@@ -43,6 +43,10 @@
  * with U and V (batch resident in HBM): the time, the largest sweep count, and the worst ||A - U S V^T||_F / ||A||_F over the batch
  * (formed on the host).
  *
+ * `./qr_device m n --batched count --minnorm` does nothing else either: m n is read as a wide shape (m <= n), `count` seeded m x n
+ * matrices and one right-hand side each (resident in HBM) go through one qr_gels_wide_batched_dev call: the time, the worst
+ * ||A x - b|| / (||A|| ||x||) and the worst distance of x from the row space of A.
+ *
  * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
  * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
  * qr_lsacc_batched_slide_dev for the whole batch -- beside one qr_gels_batched_dev per window on copies of the windows: both wall times
@@ -712,9 +716,106 @@ static int batched_svd_main(int m, int n, int count)
     return noconv ? 1 : 0;
 }
 
+/* count wide matrices of m x n through one batched minimum-norm call */
+static int batched_minnorm_main(int m, int n, int count)
+{
+    if (m < 1 || m > QR_BATCHED_MAX_N || n < m || count < 1) {
+        fprintf(stderr, "--batched count --minnorm needs count >= 1 and 1 <= m <= %d, m <= n\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d matrices of %dx%d\n", count, m, n);
+    const size_t mn = (size_t) m * n, cnt = mn * count;
+    double *A = malloc(sizeof(double) * cnt), *B = malloc(sizeof(double) * (size_t) n * count), *X = malloc(sizeof(double) * (size_t) n * count);
+    double *F = malloc(sizeof(double) * cnt), *W = malloc(sizeof(double) * (size_t) n);
+    int* info = malloc(sizeof(int) * (size_t) count);
+    if (!A || !B || !X || !F || !W || !info) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    for (int q = 0; q < count; q++)          /* dB is n rows tall: the right-hand side on top of zeros */
+        for (int i = 0; i < n; i++) B[(size_t) q * n + i] = i < m ? (double) rand() / RAND_MAX - 0.5 : 0.0;
+    qr_plan* p = NULL;
+    double *dA = NULL, *dF = NULL, *dB = NULL, *dtau = NULL;
+    int* dinfo = NULL;
+    if (qr_plan_create(&p, n, m, 0, 0) || qr_device_malloc((void**) &dA, sizeof(double) * cnt) || qr_device_malloc((void**) &dF, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dB, sizeof(double) * (size_t) n * count) || qr_device_malloc((void**) &dtau, sizeof(double) * (size_t) m * count) ||
+        qr_device_malloc((void**) &dinfo, sizeof(int) * (size_t) count) || qr_copy_to_device(dA, A, sizeof(double) * cnt)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dB, B, sizeof(double) * (size_t) n * count)) { fprintf(stderr, "copy failed\n"); return 1; }
+        const double t0 = now();
+        int rc = qr_gels_wide_batched_dev(p, dA, m, n, m, (long long) mn, dF, n, (long long) mn, dtau, m, dB, 1, n, n, dinfo, count);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc) {
+            fprintf(stderr, "qr_gels_wide_batched_dev failed: %s%s\n", qr_strerror(rc), rc == QR_E_ARG ? " (the transpose does not fit the LDS: see qr_batched_max_rows)" : "");
+            return 1;
+        }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(X, dB, sizeof(double) * (size_t) n * count) || qr_copy_to_host(F, dF, sizeof(double) * cnt) ||
+        qr_copy_to_host(info, dinfo, sizeof(int) * (size_t) count)) {
+        fprintf(stderr, "copy back failed\n");
+        return 1;
+    }
+    int singular = 0;
+    double worst = 0.0, worst_row = 0.0;
+    for (int q = 0; q < count; q++) {
+        if (info[q]) { singular++; continue; }
+        const double *a = A + q * mn, *b = B + (size_t) q * n, *x = X + (size_t) q * n;
+        double na = 0.0, nx = 0.0, nr = 0.0;
+        for (size_t i = 0; i < mn; i++) na += a[i] * a[i];
+        for (int j = 0; j < n; j++) nx += x[j] * x[j];
+        for (int i = 0; i < m; i++) {
+            double s = -b[i];
+            for (int j = 0; j < n; j++) s += a[(size_t) j * m + i] * x[j];
+            nr += s * s;
+        }
+        const double den = sqrt(na) * sqrt(nx);
+        if (den > 0.0 && sqrt(nr) / den > worst) worst = sqrt(nr) / den;
+        /* the distance of x from the row space of A: x minus its projection on the rows, by modified Gram-Schmidt twice over */
+        double* rows = F + q * mn;            /* (the factors are needed no more: m orthonormalised rows of n entries each) */
+        for (int i = 0; i < m; i++) {
+            double* ri = rows + (size_t) i * n;
+            for (int j = 0; j < n; j++) ri[j] = a[(size_t) j * m + i];
+            for (int pass = 0; pass < 2; pass++)
+                for (int k = 0; k < i; k++) {
+                    const double* rk = rows + (size_t) k * n;
+                    double d = 0.0;
+                    for (int j = 0; j < n; j++) d += rk[j] * ri[j];
+                    for (int j = 0; j < n; j++) ri[j] -= d * rk[j];
+                }
+            double nn = 0.0;
+            for (int j = 0; j < n; j++) nn += ri[j] * ri[j];
+            nn = sqrt(nn);
+            for (int j = 0; j < n; j++) ri[j] = nn > 0.0 ? ri[j] / nn : 0.0;
+        }
+        memcpy(W, x, sizeof(double) * (size_t) n);
+        for (int pass = 0; pass < 2; pass++)
+            for (int k = 0; k < m; k++) {
+                const double* rk = rows + (size_t) k * n;
+                double d = 0.0;
+                for (int j = 0; j < n; j++) d += rk[j] * W[j];
+                for (int j = 0; j < n; j++) W[j] -= d * rk[j];
+            }
+        double nw = 0.0;
+        for (int j = 0; j < n; j++) nw += W[j] * W[j];
+        if (nx > 0.0 && sqrt(nw / nx) > worst_row) worst_row = sqrt(nw / nx);
+    }
+    printf(" MMQR ran minimum-norm solves of %d %dx%d systems in %f s (avg over %d)   [batch resident in HBM, one right-hand side each]\n", count,
+           m, n, el / TRIALS, TRIALS);
+    printf(" singular = %d   worst ||A x - b|| / (||A|| ||x||) = %.2e   worst distance of x from the row space / ||x|| = %.2e\n", singular, worst,
+           worst_row);
+    qr_device_free(dA); qr_device_free(dF); qr_device_free(dB); qr_device_free(dtau); qr_device_free(dinfo);
+    qr_plan_destroy(p);
+    free(A); free(B); free(X); free(F); free(W); free(info);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -735,6 +836,8 @@ int main(int argc, char** argv)
                                               k + 1 < argc && argv[k + 1][0] != '-' ? atoi(argv[k + 1]) : atoi(argv[2]));
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--svd") == 0) return batched_svd_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--minnorm") == 0) return batched_minnorm_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             return batched_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
         }
     for (int i = 3; i < argc; i++)

@@ -880,6 +880,75 @@ int qr_lsacc_batched_destroy(qr_lsacc_batched* acc);
 int qr_lstsq_rolling_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, int window, int step,
                              double* X, double* resid, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8e. Batched minimum-norm solutions: transposed and wide systems.  Section 5 for every member of a batch -- underdetermined fits,
+ * redundant-manipulator inverse kinematics (a 6 x 7 Jacobian per sample), constraint projection per element, minimum-norm
+ * interpolation weights; what torch.linalg.lstsq on a batch of wide matrices is used for.  With F = Q R (rows x cols, rows >= cols,
+ * full rank) the minimum-norm solution of F^T X = B is X = Q [R^-T B ; 0]; a wide system A X = B is the same thing with F = A^T.
+ * Throughout, (rows, cols) is the shape of the tall matrix that is factored: (m, n) for gels_t and minnorm, (n, m) for gels_wide.
+ *
+ * Section 8's conventions hold unchanged: member q at base + q * stride, column-major, strides in elements; the plan supplies the
+ * stream only; no call waits on the host; bad arguments return QR_E_ARG before anything touches a device (what section 8 rejects, and
+ * besides: m < n or m > n where the call wants the other, ldb below the taller of B and X, ldf < n, strideF < ldf * m, dinfo, dF or
+ * dtau NULL); batch == 0 returns 0 after the checks and launches nothing; no atomics, every sum in an order that (rows, cols, nrhs)
+ * alone fix; results bitwise repeatable and bitwise independent of `batch` and of a member's index; the route follows from the shape
+ * alone.
+ *
+ * Routes.  The fused calls hold the right-hand sides beside the matrix as nrhs more columns of height rows: one wave per member (four
+ * members per workgroup) for rows <= 64 and cols + nrhs <= 32, otherwise one workgroup per member with [F | X] in LDS.  The
+ * factorisation step is section 8's, operation for operation, and does not touch the right-hand sides: dA / dtau of
+ * qr_gels_t_batched_dev and dF / dtau of qr_gels_wide_batched_dev are bitwise those of qr_geqrf_batched_dev (on the same matrix, on the
+ * explicit transpose) whenever (rows, cols) and (rows, cols + nrhs) take the same route, and always on the composed routes.  Then
+ * R^T y = b by forward substitution, y_k = (b_k - sum_{l<k} R(l,k) y_l) / R(k,k) with l ascending, and X = H_0 .. H_{cols-1} [y ; 0]
+ * with the reflectors applied cols-1 down to 0, rows >= cols starting at exact zero and tau == 0 reflectors skipped (a square
+ * member's last column, and a 1 x 1, stay exact).
+ *
+ * The info word: dinfo[q] is 0, or i + 1 for the smallest i with R(i,i) == 0 exactly (a zero row of a wide A, a zero column of F).
+ * Such a member is all or nothing, as in section 8d: its dB is bitwise what it was on entry, every row included; its factors are
+ * still written by the factoring calls; the other members are unaffected and the call returns 0.  Dependence to rounding is NOT
+ * detected: as for qr_gels_batched_dev, a member that is rank-deficient only to rounding gets a huge X and info == 0.
+ *
+ * Out of scope: rank-deficient wide systems (they need a pivoted wide factorisation and a complete orthogonal decomposition for
+ * m < n); blocked / MFMA variants; the entry points of sections 8 to 8d are unchanged and keep answering QR_E_ARG for m < n.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The solve from factors that exist (m >= n), in the layout of qr_geqrf_batched_dev or qr_geqp3_batched_dev (for pivoted factors the
+ * system solved is (A P)^T X = B): factor once, solve many.  dB is m x nrhs per member, ldb >= m, any nrhs >= 1: rows 0..n-1 hold B on
+ * entry, rows n..m-1 are ignored; on return dB = X = Q [R^-T B ; 0].  One launch for any nrhs. */
+int qr_minnorm_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda, long long strideA,
+                           const double* dtau, long long stridetau,
+                           double* dB, int nrhs, int ldb, long long strideB, int* dinfo, int batch);
+
+/* LAPACK dgels ('T', m >= n) per member: dA is factored in place (R, V, dtau as qr_geqrf_batched_dev leaves them), then the above.  One
+ * fused launch when n + nrhs <= QR_BATCHED_MAX_N and m <= qr_batched_max_rows(n + nrhs) (or m x (n + nrhs) passes section 8's
+ * narrower-fit rule); otherwise qr_geqrf_batched_dev followed by qr_minnorm_batched_dev: two launches. */
+int qr_gels_t_batched_dev(qr_plan* plan, double* dA, int m, int n, int lda, long long strideA,
+                          double* dtau, long long stridetau,
+                          double* dB, int nrhs, int ldb, long long strideB, int* dinfo, int batch);
+
+/* dD_q (cols x rows, ldd >= cols) = dS_q^T (dS_q: rows x cols, lds >= rows) for every member, out of place; nothing outside the
+ * cols x rows block is written.  Any shape with rows, cols <= 512.  Reads and writes both run along contiguous addresses, through LDS.
+ * It serves the composed wide route, and lets a caller reach dgels 'T' of a wide matrix as transpose plus qr_gels_batched_dev. */
+int qr_transpose_batched_dev(qr_plan* plan, const double* dS, int rows, int cols, int lds, long long strideS,
+                             double* dD, int ldd, long long strideD, int batch);
+
+/* LAPACK dgels ('N', m <= n) per member: the minimum-norm solution of A X = B.  m <= QR_BATCHED_MAX_N, and n x m must fit as section 8
+ * describes: n <= qr_batched_max_rows(m), or m < 64 and n rows of m columns pass the narrower-fit rule (64 x 256 and 40 x 300 are
+ * taken, 64 x 257 and 64 x 300 are not).  dA (m x n, lda >= m) is not modified.  dF (n x m, ldf >= n, strideF >= ldf * m) and dtau
+ * (m per member) receive the factors of A^T in qr_geqrf_batched_dev's layout: qr_minnorm_batched_dev(plan, dF, n, m, ...) solves
+ * again.  dB is n x nrhs, ldb >= n: rows 0..m-1 hold B on entry; on return it holds X.  One fused launch when
+ * m + nrhs <= QR_BATCHED_MAX_N and n x (m + nrhs) fits: the kernel reads A through the transposed index map straight into registers /
+ * LDS.  Otherwise transpose, geqrf, minnorm: three launches. */
+int qr_gels_wide_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda, long long strideA,
+                             double* dF, int ldf, long long strideF, double* dtau, long long stridetau,
+                             double* dB, int nrhs, int ldb, long long strideB, int* dinfo, int batch);
+
+/* The wide call on a packed batch on host pointers (A: m x n, B: m x nrhs per member, m <= n, both untouched): X n x nrhs per member,
+ * info[batch] as dinfo above.  Returns QR_E_SINGULAR if any info entry is non-zero (X of such a member holds no solution; the others
+ * are valid); QR_E_ARG for m > n.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_minnorm_batched(const double* A, int m, int n, const double* B, int nrhs, int batch,
+                             double* X, int* info);
+
 #ifdef __cplusplus
 }
 #endif
