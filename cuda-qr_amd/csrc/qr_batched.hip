@@ -10,31 +10,20 @@
 //   b_trsm_kernel      R X = B per matrix, one thread per right-hand side, and the info word (the composed route of gels)
 //   bp_*               the same with column pivoting (section 8b), further down
 //
+// The Householder column step of either route, the solves and the wave helpers are qr_batched_dev.h's (qb_*), shared with the pivoted
+// kernels below and with qr_batched_minnorm.hip; a kernel adds its loads and stores, its tau store and what it does between steps.
+//
 // Both factorisation kernels take `nrhs` extra columns from B that are updated but never factored (the fused gels: B <- Q^T B) and
 // then run the back substitution in the same launch.  LAPACK dgeqr2 / dlarfg per column: beta = -sign(alpha) hypot(alpha,
 // |x|), tau = (beta - alpha) / beta, v = x / (alpha - beta); x == 0 exactly: tau = 0, the column unchanged.
 //
 // Every sum runs in a fixed order that depends on (m, n, nrhs) alone (wave butterflies, waves added in wave order, serial loops):
 // repeated launches are bitwise equal and a matrix's result does not depend on the batch count or its index.  No atomics.
-#include <atomic>
-
-#include "qr_common.h"
-#include "qr_device.h"
+#include "qr_batched_dev.h"
 
 #define B_MAXN QRD_B_MAX_N
 
 static_assert(QRD_B_MAX_N == 64, "the routes below assume at most 64 columns in LDS");
-
-// the same sum in every lane; the order of the additions does not depend on the data
-__device__ __forceinline__ double b_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// the smallest leading dimension >= m that is 2 mod 32 (conflict-free column-major LDS image, see qr_update.hip)
-__host__ __device__ __forceinline__ int b_ld(int m) { return ((m + 29) / 32) * 32 + 2; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // wave route.  Dynamic LDS is used by the fused solve only: per wave R (W x (W + 1)) and the right-hand sides (W x (W + 1)).
@@ -63,35 +52,14 @@ __global__ void __launch_bounds__(256) b_wave_kernel(double* __restrict__ A, int
     double tauv = 0.0, diag = 1.0;            // lane j: tau[j] and R(j, j)
 #pragma unroll
     for (int j = 0; j < W; ++j) {
-        if (j < n) {                          // (wave-uniform)
-            const double x = lane > j ? a[j] : 0.0;          // (rows >= m hold zeros)
-            const double ssq = b_wave_sum(x * x);
-            const double alpha = __shfl(a[j], j);
-            double tj = 0.0;
-            if (ssq != 0.0) {
-                const double beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
-                const double scal = 1.0 / (alpha - beta);
-                tj = (beta - alpha) / beta;
-                const double v = lane > j ? a[j] * scal : (lane == j ? 1.0 : 0.0);
-#pragma unroll
-                for (int c = j + 1; c < W; ++c) {
-                    if (c < ntot) {
-                        const double tw = tj * b_wave_sum(v * a[c]);
-                        a[c] = fma(-tw, v, a[c]);
-                    }
-                }
-                a[j] = lane > j ? v : (lane == j ? beta : a[j]);
-            }
-            if (lane == j) { tauv = tj; diag = a[j]; }
-        }
+        if (j < n) qb_wave_col<W>(a, j, ntot, lane, tauv, diag);      // (wave-uniform; B's columns ride along)
     }
 #pragma unroll
     for (int c = 0; c < W; ++c)
         if (row && c < n) Aq[(size_t) c * lda + lane] = a[c];
     if (lane < n) tau[q * stridetau + lane] = tauv;
     if (!nrhs) return;
-    const unsigned long long z = __ballot(lane < n && diag == 0.0);
-    const int inf = z ? __ffsll((long long) z) : 0;
+    const int inf = qb_info_wave(diag, n, lane);
     if (lane == 0) info[q] = inf;
     if (inf) {                                // B <- Q^T B, no solve
 #pragma unroll
@@ -112,28 +80,17 @@ __global__ void __launch_bounds__(256) b_wave_kernel(double* __restrict__ A, int
             else if (row) Bq[(size_t) (c - n) * ldb + lane] = a[c];
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < nrhs) {                        // (nrhs < W <= 32: one lane per right-hand side)
-        double* xr = Xs + lane * LW;
-        for (int k = n - 1; k >= 0; --k) {
-            double s = xr[k];
-            for (int l = k + 1; l < n; ++l) s = fma(-Rs[l * LW + k], xr[l], s);
-            xr[k] = s / Rs[k * LW + k];
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    QB_WAVE_SYNC();
+    if (lane < nrhs) qb_trsv(Rs, LW, n, Xs + lane * LW);      // (nrhs < W <= 32: one lane per right-hand side)
+    QB_WAVE_SYNC();
     for (int r = 0; r < nrhs; ++r)
         if (lane < n) Bq[(size_t) r * ldb + lane] = Xs[r * LW + lane];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// workgroup route.  LDS: As[c * ld + i] = column c of [A | B], ld = b_ld(m); then red[4], a word for info, 3 spare.
+// workgroup route.  LDS: As[c * ld + i] = column c of [A | B], ld = qb_ld(m); then red[4], a word for info, 3 spare.
 // ---------------------------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ size_t b_wg_lds(int m, int ntot) { return sizeof(double) * ((size_t) ntot * b_ld(m) + 8); }
+__host__ __device__ __forceinline__ size_t b_wg_lds(int m, int ntot) { return sizeof(double) * ((size_t) ntot * qb_ld(m) + 8); }
 
 __global__ void __launch_bounds__(256) b_wg_kernel(double* __restrict__ A, int m, int n, int lda, size_t strideA, double* __restrict__ tau,
                                                    size_t stridetau, double* __restrict__ B, int nrhs, int ldb, size_t strideB,
@@ -142,7 +99,7 @@ __global__ void __launch_bounds__(256) b_wg_kernel(double* __restrict__ A, int m
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const size_t q = blockIdx.x;
-    const int ld = b_ld(m), ntot = n + nrhs;
+    const int ld = qb_ld(m), ntot = n + nrhs;
     double* As = sm;
     double* red = As + (size_t) ntot * ld;
     int* sinfo = (int*) (red + 4);
@@ -155,57 +112,17 @@ __global__ void __launch_bounds__(256) b_wg_kernel(double* __restrict__ A, int m
     }
     __syncthreads();
     for (int j = 0; j < n; ++j) {
-        double* vj = As + j * ld;
-        double s = 0.0;
-        for (int i = j + 1 + t; i < m; i += 256) s = fma(vj[i], vj[i], s);
-        s = b_wave_sum(s);
-        if (lane == 0) red[wv] = s;
-        __syncthreads();
-        const double ssq = ((red[0] + red[1]) + red[2]) + red[3];
-        double tj = 0.0;
-        if (ssq != 0.0) {                     // (the same value in every thread)
-            const double alpha = vj[j];
-            const double beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
-            const double scal = 1.0 / (alpha - beta);
-            tj = (beta - alpha) / beta;
-            __syncthreads();                  // (every thread has read alpha and the column)
-            for (int i = j + 1 + t; i < m; i += 256) vj[i] *= scal;
-            if (t == 0) vj[j] = beta;
-            __syncthreads();
-            // wave wv: columns j + 1 + wv, + 4, ..: w = v^T c with the unit entry at row j, c -= tau w v
-            for (int c = j + 1 + wv; c < ntot; c += 4) {
-                double* bc = As + c * ld;
-                double d = 0.0;
-                for (int i = j + 1 + lane; i < m; i += 64) d = fma(vj[i], bc[i], d);
-                d = b_wave_sum(d);
-                const double tw = tj * (bc[j] + d);
-                for (int i = j + 1 + lane; i < m; i += 64) bc[i] = fma(-tw, vj[i], bc[i]);
-                if (lane == 0) bc[j] -= tw;   // (read by every lane above: the wave runs in lock step up to the butterfly; ordered below)
-            }
-        }
+        const double tj = qb_wg_col(As, ld, m, j, ntot, red, t);
         if (t == 0) tq[j] = tj;
         __syncthreads();                      // (red and column j are read no more)
     }
     for (int c = wv; c < n; c += 4)
         for (int i = lane; i < m; i += 64) Aq[(size_t) c * lda + i] = As[c * ld + i];
     if (!nrhs) return;
-    if (t == 0) {
-        int inf = 0;
-        for (int i = n - 1; i >= 0; --i)
-            if (As[i * ld + i] == 0.0) inf = i + 1;
-        *sinfo = inf;
-        info[q] = inf;
-    }
+    if (t == 0) info[q] = *sinfo = qb_info_serial(As, ld, n);
     __syncthreads();
     if (*sinfo == 0) {
-        if (t < nrhs) {                       // (nrhs < 64: one thread per right-hand side)
-            double* xr = As + (size_t) (n + t) * ld;
-            for (int k = n - 1; k >= 0; --k) {
-                double s = xr[k];
-                for (int l = k + 1; l < n; ++l) s = fma(-As[l * ld + k], xr[l], s);
-                xr[k] = s / As[k * ld + k];
-            }
-        }
+        if (t < nrhs) qb_trsv(As, ld, n, As + (size_t) (n + t) * ld);         // (nrhs < 64: one thread per right-hand side)
         __syncthreads();
     }
     for (int c = n + wv; c < ntot; c += 4)
@@ -220,7 +137,7 @@ __global__ void __launch_bounds__(256) b_wg_kernel(double* __restrict__ A, int m
 #define B_ROWREGS 8
 static_assert(QRD_B_MAX_ROWS <= 64 * B_ROWREGS, "a column of C is held in B_ROWREGS registers per lane");
 
-__host__ __device__ __forceinline__ size_t b_ormqr_lds(int m, int n) { return sizeof(double) * ((size_t) n * b_ld(m) + B_MAXN); }
+__host__ __device__ __forceinline__ size_t b_ormqr_lds(int m, int n) { return sizeof(double) * ((size_t) n * qb_ld(m) + B_MAXN); }
 
 template <int RR>
 __global__ void __launch_bounds__(256) b_ormqr_kernel(int tr, const double* __restrict__ A, int m, int n, int lda, size_t strideA,
@@ -230,7 +147,7 @@ __global__ void __launch_bounds__(256) b_ormqr_kernel(int tr, const double* __re
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const size_t q = blockIdx.x;
-    const int ld = b_ld(m);
+    const int ld = qb_ld(m);
     double* Vs = sm;
     double* ts = Vs + (size_t) n * ld;
     const double* Aq = A + q * strideA;
@@ -251,18 +168,7 @@ __global__ void __launch_bounds__(256) b_ormqr_kernel(int tr, const double* __re
             const int j = tr ? jj : n - 1 - jj;
             const double tj = ts[j];
             if (tj == 0.0) continue;          // (H = I; wave-uniform)
-            const double* vj = Vs + j * ld;
-            double v[RR];
-            double d = 0.0;
-#pragma unroll
-            for (int k = 0; k < RR; ++k) {
-                const int i = lane + 64 * k;
-                v[k] = (i > j && i < m) ? vj[i] : (i == j ? 1.0 : 0.0);
-                d = fma(v[k], c[k], d);
-            }
-            const double tw = tj * b_wave_sum(d);
-#pragma unroll
-            for (int k = 0; k < RR; ++k) c[k] = fma(-tw, v[k], c[k]);
+            qb_regs_reflect<RR>(Vs + j * ld, j, m, tj, c, lane);
         }
 #pragma unroll
         for (int k = 0; k < RR; ++k) {
@@ -300,43 +206,24 @@ __global__ void __launch_bounds__(256) b_trsm_kernel(const double* __restrict__ 
         Rs[c * lr + r] = r <= c ? Aq[(size_t) c * lda + r] : 0.0;
     }
     __syncthreads();
-    if (t == 0) {
-        int inf = 0;
-        for (int i = n - 1; i >= 0; --i)
-            if (Rs[i * lr + i] == 0.0) inf = i + 1;
-        *sinfo = inf;
-        info[q] = inf;
-    }
+    if (t == 0) info[q] = *sinfo = qb_info_serial(Rs, lr, n);
     __syncthreads();
     if (*sinfo) return;
-    for (int r = t; r < nrhs; r += 256) {     // (a thread owns its column of B: no other thread reads or writes it)
-        double* xr = Bq + (size_t) r * ldb;
-        for (int k = n - 1; k >= 0; --k) {
-            double s = xr[k];
-            for (int l = k + 1; l < n; ++l) s = fma(-Rs[l * lr + k], xr[l], s);
-            xr[k] = s / Rs[k * lr + k];
-        }
-    }
+    for (int r = t; r < nrhs; r += 256) qb_trsv(Rs, lr, n, Bq + (size_t) r * ldb);    // (a thread owns its column of B: no other thread touches it)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Section 8b: column pivoting.  bp_wave_kernel<W> and bp_wg_kernel are the pivoted siblings of the two factorisation kernels above
 // (LAPACK dlaqp2 per matrix: every column free, the partial norms downdated and recomputed by its rule); with nrhs > 0 they carry the
 // right-hand sides along and end with the rank-revealing solve (bp_tz_sweep, bp_solve_cols).  bp_solve_kernel is that solve on its
-// own (the composed route), bp_rank_kernel the rank from the diagonal.  The Householder step itself is restated, not shared: the
-// unpivoted kernels keep their code, and so their bits.
+// own (the composed route), bp_rank_kernel the rank from the diagonal.  The Householder step itself is the unpivoted kernels' (qb_wave_col,
+// qb_wg_col): a pivoted kernel adds the pivot search and the swap before it and the downdate of the norms after it, so on columns
+// that are already in pivot order its factors and tau are bitwise qrd_b_geqrf's.
 //
 // The norm state of column c (vn1: the running partial norm, vn2: its value when last computed exactly) and jpvt[c] live in lane c of
 // the wave (wave 0 of the workgroup route): n <= 64.  Every arg-max, swap and sum runs in an order that (m, n, nrhs) fix.
 // ---------------------------------------------------------------------------------------------------------------------------------
 #define BP_TOL3Z 1.4901161193847656e-08          // sqrt(DBL_EPSILON), dlaqp2's tol3z
-
-#define BP_WAVE_SYNC()                                           \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
-        __builtin_amdgcn_wave_barrier();                         \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
-    } while (0)
 
 // the index of the largest v over the wave, the lowest index on a tie; lanes that do not compete pass v < 0.  A butterfly on (v, idx)
 // pairs under a total order: the same pair in every lane, whatever the data.  (NaN breaks the order: the callers clamp the result.)
@@ -349,13 +236,6 @@ __device__ __forceinline__ int bp_wave_argmax(double v, int idx)
         if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
     }
     return __builtin_amdgcn_readfirstlane(idx);
-}
-
-// v of lane l, l wave-uniform: two readlanes (what __shfl spends a bpermute pair on)
-__device__ __forceinline__ double bp_bcast(double v, int l)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
 }
 
 // dlaqp2's downdate of one column after step j: a = A(j, c).  Returns true where the norm has to be recomputed from rows j+1 .. m-1.
@@ -386,17 +266,16 @@ __device__ __forceinline__ void bp_tz_sweep(double* Rs, int ldr, int n, int r, i
     const int l = n - r;
     for (int i = r - 1; i >= 0; --i) {
         const double x = lane < l ? Rs[(r + lane) * ldr + i] : 0.0;
-        const double ssq = b_wave_sum(x * x);
+        const double ssq = qb_wave_sum(x * x);
         const double alpha = Rs[i * ldr + i];
         double ti = 0.0;
         if (ssq != 0.0) {                     // (the same value in every lane)
-            const double beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
-            const double scal = 1.0 / (alpha - beta);
-            ti = (beta - alpha) / beta;
-            BP_WAVE_SYNC();                   // (every lane has read alpha and its x)
+            double beta, scal;
+            ti = qb_larfg(alpha, ssq, beta, scal);
+            QB_WAVE_SYNC();                   // (every lane has read alpha and its x)
             if (lane < l) Rs[(r + lane) * ldr + i] = x * scal;
             if (lane == 0) Rs[i * ldr + i] = beta;
-            BP_WAVE_SYNC();
+            QB_WAVE_SYNC();
             if (lane < i) {                   // lane k: row k, w = T(k,i) + R(k, r..) . v
                 double w = Rs[i * ldr + lane];
                 for (int c = 0; c < l; ++c) w = fma(Rs[(r + c) * ldr + lane], Rs[(r + c) * ldr + i], w);
@@ -404,11 +283,11 @@ __device__ __forceinline__ void bp_tz_sweep(double* Rs, int ldr, int n, int r, i
                 Rs[i * ldr + lane] -= tw;
                 for (int c = 0; c < l; ++c) Rs[(r + c) * ldr + lane] = fma(-tw, Rs[(r + c) * ldr + i], Rs[(r + c) * ldr + lane]);
             }
-            BP_WAVE_SYNC();
+            QB_WAVE_SYNC();
         }
         if (lane == 0) Rs[1 + i] = ti;
     }
-    BP_WAVE_SYNC();
+    QB_WAVE_SYNC();
 }
 
 // One wave, lane k < nrhs <= 64: column k of Xs (Xs[k * ldx + i], rows 0 .. n-1 of Q^T b) <- T11^-1 of its first r rows, zeros below,
@@ -417,11 +296,7 @@ __device__ __forceinline__ void bp_solve_cols(const double* Rs, int ldr, double*
 {
     if (lane < nrhs) {
         double* xr = Xs + (size_t) lane * ldx;
-        for (int k = r - 1; k >= 0; --k) {
-            double s = xr[k];
-            for (int c = k + 1; c < r; ++c) s = fma(-Rs[c * ldr + k], xr[c], s);
-            xr[k] = s / Rs[k * ldr + k];
-        }
+        qb_trsv(Rs, ldr, r, xr);
         for (int k = r; k < n; ++k) xr[k] = 0.0;
         if (cod) {
             for (int i = 0; i < r; ++i) {
@@ -435,7 +310,7 @@ __device__ __forceinline__ void bp_solve_cols(const double* Rs, int ldr, double*
             }
         }
     }
-    BP_WAVE_SYNC();
+    QB_WAVE_SYNC();
 }
 
 // Step J of the wave route and, while columns remain, the steps after it.  The steps are a compile-time recursion, not a loop: every
@@ -461,35 +336,17 @@ __device__ __forceinline__ void bp_wave_step(double (&a)[W], int n, int ntot, in
             }
             a[j] = ap;
             const int jpp = __builtin_amdgcn_readlane(jp, p), jpj = __builtin_amdgcn_readlane(jp, j);
-            const double v1 = bp_bcast(vn1, j), v2 = bp_bcast(vn2, j);
+            const double v1 = qb_bcast(vn1, j), v2 = qb_bcast(vn2, j);
             if (lane == j) jp = jpp;
             if (lane == p) { jp = jpj; vn1 = v1; vn2 = v2; }
         }
-        const double x = lane > j ? a[j] : 0.0;              // (rows >= m hold zeros)
-        const double ssq = b_wave_sum(x * x);
-        const double alpha = __shfl(a[j], j);
-        double tj = 0.0;
-        if (ssq != 0.0) {
-            const double beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
-            const double scal = 1.0 / (alpha - beta);
-            tj = (beta - alpha) / beta;
-            const double v = lane > j ? a[j] * scal : (lane == j ? 1.0 : 0.0);
-#pragma unroll
-            for (int c = j + 1; c < W; ++c) {
-                if (c < ntot) {
-                    const double tw = tj * b_wave_sum(v * a[c]);
-                    a[c] = fma(-tw, v, a[c]);
-                }
-            }
-            a[j] = lane > j ? v : (lane == j ? beta : a[j]);
-        }
-        if (lane == j) { tauv = tj; diag = a[j]; }
+        qb_wave_col<W>(a, j, ntot, lane, tauv, diag);
         // lane c > j: downdate with A(j, c), which lane j holds
         double ajc = 0.0;
 #pragma unroll
         for (int c = j + 1; c < W; ++c) {
             if (c < n) {
-                const double v = bp_bcast(a[c], j);
+                const double v = qb_bcast(a[c], j);
                 if (lane == c) ajc = v;
             }
         }
@@ -502,7 +359,7 @@ __device__ __forceinline__ void bp_wave_step(double (&a)[W], int n, int ntot, in
 #pragma unroll
             for (int k = j + 1; k < W; ++k) y = k == c ? a[k] : y;
             y = lane > j ? y : 0.0;
-            const double s = sqrt(b_wave_sum(y * y));
+            const double s = sqrt(qb_wave_sum(y * y));
             if (lane == c) vn1 = vn2 = s;
         }
         bp_wave_step<W, J + 1>(a, n, ntot, lane, vn1, vn2, jp, tauv, diag);
@@ -537,7 +394,7 @@ __global__ void __launch_bounds__(256) bp_wave_kernel(double* __restrict__ A, in
 #pragma unroll
     for (int c = 0; c < W; ++c) {
         if (c < n) {
-            const double s = sqrt(b_wave_sum(a[c] * a[c]));
+            const double s = sqrt(qb_wave_sum(a[c] * a[c]));
             if (lane == c) vn1 = vn2 = s;
         }
     }
@@ -557,7 +414,7 @@ __global__ void __launch_bounds__(256) bp_wave_kernel(double* __restrict__ A, in
     for (int c = 0; c < W; ++c) {
         if (c >= n && c < ntot) {
             const double y = lane >= r ? a[c] : 0.0;
-            const double s = sqrt(b_wave_sum(y * y));
+            const double s = sqrt(qb_wave_sum(y * y));
             if (resid && lane == 0) resid[q * nrhs + (c - n)] = s;
         }
     }
@@ -574,7 +431,7 @@ __global__ void __launch_bounds__(256) bp_wave_kernel(double* __restrict__ A, in
             else if (row) Bq[(size_t) (c - n) * ldb + lane] = a[c];
         }
     }
-    BP_WAVE_SYNC();
+    QB_WAVE_SYNC();
     const int cod = minnorm && r > 0 && r < n;
     if (cod) bp_tz_sweep(Rs, LW, n, r, lane);
     bp_solve_cols(Rs, LW, Xs, LW, n, r, nrhs, cod, lane);
@@ -583,8 +440,8 @@ __global__ void __launch_bounds__(256) bp_wave_kernel(double* __restrict__ A, in
 }
 
 // workgroup route.  LDS: the image As of [A | B] as b_wg_kernel, red[4], two words (the pivot, the rank), 3 spare, nrm[64] (the
-// initial norms on their way to wave 0's lanes): ntot * ld + 72 doubles, what qrd_b_fits budgets.
-__host__ __device__ __forceinline__ size_t bp_wg_lds(int m, int ntot) { return sizeof(double) * ((size_t) ntot * b_ld(m) + 72); }
+// initial norms on their way to wave 0's lanes): ntot * ld + QB_WG_SMALL doubles, what qrd_b_fits budgets.
+__host__ __device__ __forceinline__ size_t bp_wg_lds(int m, int ntot) { return sizeof(double) * ((size_t) ntot * qb_ld(m) + QB_WG_SMALL); }
 
 __global__ void __launch_bounds__(256) bp_wg_kernel(double* __restrict__ A, int m, int n, int lda, size_t strideA, int* __restrict__ jpvt,
                                                     size_t stridej, double* __restrict__ tau, size_t stridetau, double* __restrict__ B, int nrhs,
@@ -594,7 +451,7 @@ __global__ void __launch_bounds__(256) bp_wg_kernel(double* __restrict__ A, int 
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const size_t q = blockIdx.x;
-    const int ld = b_ld(m), ntot = n + nrhs;
+    const int ld = qb_ld(m), ntot = n + nrhs;
     double* As = sm;
     double* red = As + (size_t) ntot * ld;
     int* sw = (int*) (red + 4);               // sw[0]: the pivot of the step, sw[1]: the rank
@@ -610,7 +467,7 @@ __global__ void __launch_bounds__(256) bp_wg_kernel(double* __restrict__ A, int 
     for (int c = wv; c < n; c += 4) {         // the initial norms: one pass over the image
         double s = 0.0;
         for (int i = lane; i < m; i += 64) s = fma(As[c * ld + i], As[c * ld + i], s);
-        s = b_wave_sum(s);
+        s = qb_wave_sum(s);
         if (lane == 0) nrm[c] = sqrt(s);
     }
     __syncthreads();
@@ -624,15 +481,15 @@ __global__ void __launch_bounds__(256) bp_wg_kernel(double* __restrict__ A, int 
             if (lane == 0) sw[0] = p;
             if (p != j) {
                 const int jpp = __builtin_amdgcn_readlane(jp, p), jpj = __builtin_amdgcn_readlane(jp, j);
-                const double v1 = bp_bcast(vn1, j), v2 = bp_bcast(vn2, j);
+                const double v1 = qb_bcast(vn1, j), v2 = qb_bcast(vn2, j);
                 if (lane == j) jp = jpp;
                 if (lane == p) { jp = jpj; vn1 = v1; vn2 = v2; }
             }
         }
         __syncthreads();
         const int p = sw[0];
-        double* vj = As + j * ld;
         if (p != j) {                         // (the same value in every thread)
+            double* vj = As + j * ld;
             double* vp = As + p * ld;
             for (int i = t; i < m; i += 256) {
                 const double tmp = vj[i];
@@ -641,33 +498,7 @@ __global__ void __launch_bounds__(256) bp_wg_kernel(double* __restrict__ A, int 
             }
             __syncthreads();
         }
-        // the column step of b_wg_kernel
-        double s = 0.0;
-        for (int i = j + 1 + t; i < m; i += 256) s = fma(vj[i], vj[i], s);
-        s = b_wave_sum(s);
-        if (lane == 0) red[wv] = s;
-        __syncthreads();
-        const double ssq = ((red[0] + red[1]) + red[2]) + red[3];
-        double tj = 0.0;
-        if (ssq != 0.0) {
-            const double alpha = vj[j];
-            const double beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
-            const double scal = 1.0 / (alpha - beta);
-            tj = (beta - alpha) / beta;
-            __syncthreads();
-            for (int i = j + 1 + t; i < m; i += 256) vj[i] *= scal;
-            if (t == 0) vj[j] = beta;
-            __syncthreads();
-            for (int c = j + 1 + wv; c < ntot; c += 4) {
-                double* bc = As + c * ld;
-                double d = 0.0;
-                for (int i = j + 1 + lane; i < m; i += 64) d = fma(vj[i], bc[i], d);
-                d = b_wave_sum(d);
-                const double tw = tj * (bc[j] + d);
-                for (int i = j + 1 + lane; i < m; i += 64) bc[i] = fma(-tw, vj[i], bc[i]);
-                if (lane == 0) bc[j] -= tw;
-            }
-        }
+        const double tj = qb_wg_col(As, ld, m, j, ntot, red, t);
         if (t == 0) tq[j] = tj;
         __syncthreads();
         // wave 0 alone, while the others wait at the next step's barrier: lane c > j downdates with A(j, c); the columns that trip the
@@ -681,7 +512,7 @@ __global__ void __launch_bounds__(256) bp_wg_kernel(double* __restrict__ A, int 
                 mask &= mask - 1;
                 double y = 0.0;
                 for (int i = j + 1 + lane; i < m; i += 64) y = fma(As[c * ld + i], As[c * ld + i], y);
-                y = sqrt(b_wave_sum(y));
+                y = sqrt(qb_wave_sum(y));
                 if (lane == c) vn1 = vn2 = y;
             }
         }
@@ -703,7 +534,7 @@ __global__ void __launch_bounds__(256) bp_wg_kernel(double* __restrict__ A, int 
         for (int c = n + wv; c < ntot; c += 4) {
             double y = 0.0;
             for (int i = r + lane; i < m; i += 64) y = fma(As[c * ld + i], As[c * ld + i], y);
-            y = sqrt(b_wave_sum(y));
+            y = sqrt(qb_wave_sum(y));
             if (lane == 0) resid[q * nrhs + (c - n)] = y;
         }
     __syncthreads();
@@ -741,7 +572,7 @@ __global__ void __launch_bounds__(64) bp_solve_kernel(const double* __restrict__
     }
     int jp = lane < n ? jpvt[q * stridej + lane] : 0;
     if (jp < 0 || jp >= n) jp = lane < n ? lane : 0;          // (a jpvt that is none of geqp3's must not carry a store out of the block)
-    BP_WAVE_SYNC();
+    QB_WAVE_SYNC();
     const int r = bp_wave_rank(lane < n ? Rs[lane * lr + lane] : 0.0, n, lane, rcond);
     if (rank && blockIdx.y == 0 && lane == 0) rank[q] = r;
     const int cod = minnorm && r > 0 && r < n;
@@ -752,15 +583,15 @@ __global__ void __launch_bounds__(64) bp_solve_kernel(const double* __restrict__
             const double* col = Bq + (size_t) (k0 + k) * ldb;
             double y = 0.0;
             for (int i = r + lane; i < m; i += 64) y = fma(col[i], col[i], y);
-            y = sqrt(b_wave_sum(y));
+            y = sqrt(qb_wave_sum(y));
             if (resid && lane == 0) resid[q * nrhs + (k0 + k)] = y;
             if (lane < n) Xs[k * lr + lane] = col[lane];
         }
-        BP_WAVE_SYNC();
+        QB_WAVE_SYNC();
         bp_solve_cols(Rs, lr, Xs, lr, n, r, nk, cod, lane);
         for (int k = 0; k < nk; ++k)
             if (lane < n) Bq[(size_t) (k0 + k) * ldb + jp] = Xs[k * lr + lane];
-        BP_WAVE_SYNC();                       // (Xs is read no more)
+        QB_WAVE_SYNC();                       // (Xs is read no more)
     }
 }
 
@@ -777,34 +608,16 @@ __global__ void __launch_bounds__(256) bp_rank_kernel(const double* __restrict__
     rank[q] = r;
 }
 
-// more than 64 KiB of LDS per workgroup has to be allowed per kernel and device, once
+// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
 static int b_allow_lds(void)
 {
     static std::atomic<int> done[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int) e;
-    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
-    const int cap = 160 * 1024;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(b_wg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(b_ormqr_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(b_ormqr_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(b_ormqr_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(b_ormqr_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(b_wave_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_wg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_wave_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bp_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess && dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
-    return (int) e;
+    const void* const fns[] = {reinterpret_cast<const void*>(b_wg_kernel),       reinterpret_cast<const void*>(b_ormqr_kernel<1>),
+                               reinterpret_cast<const void*>(b_ormqr_kernel<2>), reinterpret_cast<const void*>(b_ormqr_kernel<4>),
+                               reinterpret_cast<const void*>(b_ormqr_kernel<8>), reinterpret_cast<const void*>(b_wave_kernel<32>),
+                               reinterpret_cast<const void*>(bp_wg_kernel),      reinterpret_cast<const void*>(bp_wave_kernel<32>),
+                               reinterpret_cast<const void*>(bp_solve_kernel)};
+    return qb_allow_lds(fns, done);
 }
 
 template <int W>
@@ -834,11 +647,12 @@ int qrd_b_max_rows(int ncols)
     return ncols <= 32 ? QRD_B_MAX_ROWS : QRD_B_MAX_ROWS / 2;
 }
 
-// what the kernels hold: at most QRD_B_MAX_ROWS rows (b_ormqr_kernel's registers) and ncols columns at b_ld(m) plus the small arrays
-// (72 doubles cover both b_wg_kernel and b_ormqr_kernel) within 160 KiB of LDS.  Every shape within qrd_b_max_rows fits.
+// what the kernels hold: at most QRD_B_MAX_ROWS rows (b_ormqr_kernel's registers) and ncols columns at qb_ld(m) plus the small arrays
+// (QB_WG_SMALL doubles cover b_wg_kernel and b_ormqr_kernel too) within QB_LDS_CAP.  Every shape within qrd_b_max_rows fits.
 int qrd_b_fits(int m, int ncols)
 {
-    return ncols >= 1 && ncols <= QRD_B_MAX_N && m >= 1 && m <= QRD_B_MAX_ROWS && sizeof(double) * ((size_t) ncols * b_ld(m) + 72) <= 160 * 1024;
+    return ncols >= 1 && ncols <= QRD_B_MAX_N && m >= 1 && m <= QRD_B_MAX_ROWS &&
+           sizeof(double) * ((size_t) ncols * qb_ld(m) + QB_WG_SMALL) <= QB_LDS_CAP;
 }
 
 int qrd_b_wave_route(int m, int ncols) { return m <= 64 && ncols <= 32; }

@@ -2,11 +2,11 @@
 // (rows x cols, rows >= cols, full rank) the minimum-norm solution of F^T X = B is X = Q [R^-T B ; 0], per member of a batch.
 //
 //   bm_wave_kernel<W, TR>  rows <= 64, cols + nrhs <= W <= 32: one wave per member, four members per workgroup.  Lane i holds row i of F
-//                      in W registers; the factorisation is b_wave_kernel's (qr_batched.hip) column step restated, the right-hand sides
-//                      untouched by it; then R^T y = b on an LDS image of R, one lane per right-hand side, and the reflectors
+//                      in W registers; the factorisation is b_wave_kernel's (qr_batched.hip) column step, qb_wave_col, the right-hand
+//                      sides untouched by it; then R^T y = b on an LDS image of R, one lane per right-hand side, and the reflectors
 //                      cols-1 .. 0 on [y ; 0] with the column back in registers, one butterfly each
 //   bm_wg_kernel       everything else that holds cols + nrhs columns in LDS: one workgroup per member, [F | X] resident at
-//                      ld = bm_ld(rows); b_wg_kernel's column step restated; then the same two stages, wave w on right-hand sides
+//                      ld = qb_ld(rows); b_wg_kernel's column step, qb_wg_col; then the same two stages, wave w on right-hand sides
 //                      w, w + 4, ..
 //   bm_apply_kernel<RR> the solve on factors that exist (any nrhs): grid (batch, groups of 16 right-hand sides), whole columns of the factors
 //                      in LDS, one wave per right-hand side with the column in registers
@@ -15,46 +15,17 @@
 // TR (bm_wave_kernel) / tr (bm_wg_kernel): the member is given as the wide matrix A = F^T (cols x rows, column-major), read through the
 // transposed index map, F (A, lda) -> (A^T); the factors then go to a buffer of their own.  Otherwise F is factored in place.
 //
-// The two factorisation loops are b_wave_kernel's and b_wg_kernel's operation for operation (the same butterflies, the same 256-thread
-// strided norm with four wave partials added in wave order, the same fmas) over the first `cols` columns only: the factors and tau are
-// bitwise those of qrd_b_geqrf on the same route.  Every sum runs in an order that (rows, cols, nrhs) fix; no atomics.
+// The two factorisation loops call the column steps that b_wave_kernel and b_wg_kernel call (qr_batched_dev.h), with the end of the
+// update at `cols` where those pass cols + nrhs: the factors and tau are bitwise those of qrd_b_geqrf on the same route.  The callers
+// add the transposed load, the copy of tau kept in LDS and the solve.  Every sum runs in an order that (rows, cols, nrhs) fix; no atomics.
 //
 // info: 0, or i + 1 for the smallest i with R(i,i) == 0 exactly; such a member's right-hand sides are not written at all.
-#include <atomic>
-
-#include "qr_common.h"
-#include "qr_device.h"
+#include "qr_batched_dev.h"
 
 #define BM_MAXN QRD_B_MAX_N
-#define BM_LDS_CAP (160 * 1024)
 #define BM_COLS 16                        // right-hand sides per workgroup of bm_apply_kernel: four per wave
 
 static_assert(QRD_B_MAX_N == 64, "the forward substitution of bm_apply_kernel holds one row of R^T y = b per lane");
-
-// the same sum in every lane; the order of the additions does not depend on the data (b_wave_sum of qr_batched.hip)
-__device__ __forceinline__ double bm_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// v of lane l, l wave-uniform
-__device__ __forceinline__ double bm_bcast(double v, int l)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-// the smallest leading dimension >= m that is 2 mod 32 (b_ld of qr_batched.hip: what qrd_b_fits budgets)
-__host__ __device__ __forceinline__ int bm_ld(int m) { return ((m + 29) / 32) * 32 + 2; }
-
-#define BM_WAVE_SYNC()                                           \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
-        __builtin_amdgcn_wave_barrier();                         \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // wave route.  Dynamic LDS per wave: Rs (W x (W + 1), Rs[c * LW + r] = R(r, c)) and Xs (W x (W + 1), Xs[k * LW + r] = b_k(r), then y).
@@ -82,37 +53,15 @@ __global__ void __launch_bounds__(256) bm_wave_kernel(const double* A, int m, in
         a[c] = v;
     }
     double tauv = 0.0, diag = 1.0;            // lane j: tau[j] and R(j, j)
-    // the column step of b_wave_kernel over the n columns of F
 #pragma unroll
     for (int j = 0; j < W; ++j) {
-        if (j < n) {                          // (wave-uniform)
-            const double x = lane > j ? a[j] : 0.0;          // (rows >= m hold zeros)
-            const double ssq = bm_wave_sum(x * x);
-            const double alpha = __shfl(a[j], j);
-            double tj = 0.0;
-            if (ssq != 0.0) {
-                const double beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
-                const double scal = 1.0 / (alpha - beta);
-                tj = (beta - alpha) / beta;
-                const double v = lane > j ? a[j] * scal : (lane == j ? 1.0 : 0.0);
-#pragma unroll
-                for (int c = j + 1; c < W; ++c) {
-                    if (c < n) {
-                        const double tw = tj * bm_wave_sum(v * a[c]);
-                        a[c] = fma(-tw, v, a[c]);
-                    }
-                }
-                a[j] = lane > j ? v : (lane == j ? beta : a[j]);
-            }
-            if (lane == j) { tauv = tj; diag = a[j]; }
-        }
+        if (j < n) qb_wave_col<W>(a, j, n, lane, tauv, diag);         // (wave-uniform; the update ends at n: the right-hand sides are not in a[] yet)
     }
 #pragma unroll
     for (int c = 0; c < W; ++c)
         if (row && c < n) Fq[(size_t) c * ldf + lane] = a[c];
     if (lane < n) tau[q * stridetau + lane] = tauv;
-    const unsigned long long z = __ballot(lane < n && diag == 0.0);
-    const int inf = z ? __ffsll((long long) z) : 0;
+    const int inf = qb_info_wave(diag, n, lane);
     if (lane == 0) info[q] = inf;
     if (inf) return;                          // (all or nothing: B is as it was)
     // staging: R and rows 0 .. n-1 of B into this wave's LDS
@@ -124,16 +73,9 @@ __global__ void __launch_bounds__(256) bm_wave_kernel(const double* A, int m, in
         if (c < n && lane < n) Rs[c * LW + lane] = a[c];
     for (int k = 0; k < nrhs; ++k)
         if (lane < n) Xs[k * LW + lane] = Bq[(size_t) k * ldb + lane];
-    BM_WAVE_SYNC();
-    if (lane < nrhs) {                        // (nrhs < W <= 32: one lane per right-hand side) R^T y = b, l ascending
-        double* xr = Xs + lane * LW;
-        for (int k = 0; k < n; ++k) {
-            double s = xr[k];
-            for (int l = 0; l < k; ++l) s = fma(-Rs[k * LW + l], xr[l], s);
-            xr[k] = s / Rs[k * LW + k];
-        }
-    }
-    BM_WAVE_SYNC();
+    QB_WAVE_SYNC();
+    if (lane < nrhs) qb_trsv_t(Rs, LW, n, Xs + lane * LW);    // (nrhs < W <= 32: one lane per right-hand side) R^T y = b
+    QB_WAVE_SYNC();
     // [y ; 0] back into the registers beside F, then H_0 .. H_{n-1} applied last first: one butterfly per reflector and column
 #pragma unroll
     for (int c = 0; c < W; ++c)
@@ -148,7 +90,7 @@ __global__ void __launch_bounds__(256) bm_wave_kernel(const double* A, int m, in
 #pragma unroll
                 for (int c = j + 1; c < W; ++c) {
                     if (c >= n && c < ntot) {
-                        const double tw = tj * bm_wave_sum(v * a[c]);
+                        const double tw = tj * qb_wave_sum(v * a[c]);
                         a[c] = fma(-tw, v, a[c]);
                     }
                 }
@@ -161,10 +103,10 @@ __global__ void __launch_bounds__(256) bm_wave_kernel(const double* A, int m, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// workgroup route.  LDS: As[c * ld + i] = column c of [F | X], ld = bm_ld(m); then red[4], a word for info, 3 spare, ts[64] (tau):
-// (n + nrhs) * ld + 72 doubles, what qrd_b_fits budgets.
+// workgroup route.  LDS: As[c * ld + i] = column c of [F | X], ld = qb_ld(m); then red[4], a word for info, 3 spare, ts[64] (tau):
+// (n + nrhs) * ld + QB_WG_SMALL doubles, what qrd_b_fits budgets.
 // ---------------------------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ size_t bm_wg_lds(int m, int ntot) { return sizeof(double) * ((size_t) ntot * bm_ld(m) + 72); }
+__host__ __device__ __forceinline__ size_t bm_wg_lds(int m, int ntot) { return sizeof(double) * ((size_t) ntot * qb_ld(m) + QB_WG_SMALL); }
 
 __global__ void __launch_bounds__(256) bm_wg_kernel(int tr, const double* A, int m, int n, int lda, size_t strideA, double* F, int ldf,
                                                     size_t strideF, double* __restrict__ tau, size_t stridetau, double* __restrict__ B, int nrhs,
@@ -173,7 +115,7 @@ __global__ void __launch_bounds__(256) bm_wg_kernel(int tr, const double* A, int
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const size_t q = blockIdx.x;
-    const int ld = bm_ld(m), ntot = n + nrhs;
+    const int ld = qb_ld(m), ntot = n + nrhs;
     double* As = sm;
     double* red = As + (size_t) ntot * ld;
     int* sinfo = (int*) (red + 4);
@@ -198,57 +140,17 @@ __global__ void __launch_bounds__(256) bm_wg_kernel(int tr, const double* A, int
         for (int i = lane; i < m; i += 64) As[c * ld + i] = i < n ? src[i] : 0.0;
     }
     __syncthreads();
-    // the column step of b_wg_kernel over the n columns of F
     for (int j = 0; j < n; ++j) {
-        double* vj = As + j * ld;
-        double s = 0.0;
-        for (int i = j + 1 + t; i < m; i += 256) s = fma(vj[i], vj[i], s);
-        s = bm_wave_sum(s);
-        if (lane == 0) red[wv] = s;
-        __syncthreads();
-        const double ssq = ((red[0] + red[1]) + red[2]) + red[3];
-        double tj = 0.0;
-        if (ssq != 0.0) {                     // (the same value in every thread)
-            const double alpha = vj[j];
-            const double beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
-            const double scal = 1.0 / (alpha - beta);
-            tj = (beta - alpha) / beta;
-            __syncthreads();                  // (every thread has read alpha and the column)
-            for (int i = j + 1 + t; i < m; i += 256) vj[i] *= scal;
-            if (t == 0) vj[j] = beta;
-            __syncthreads();
-            for (int c = j + 1 + wv; c < n; c += 4) {
-                double* bc = As + c * ld;
-                double d = 0.0;
-                for (int i = j + 1 + lane; i < m; i += 64) d = fma(vj[i], bc[i], d);
-                d = bm_wave_sum(d);
-                const double tw = tj * (bc[j] + d);
-                for (int i = j + 1 + lane; i < m; i += 64) bc[i] = fma(-tw, vj[i], bc[i]);
-                if (lane == 0) bc[j] -= tw;   // (read by every lane above: the wave runs in lock step up to the butterfly; ordered below)
-            }
-        }
+        const double tj = qb_wg_col(As, ld, m, j, n, red, t);         // (the update ends at n: the right-hand sides take no part)
         if (t == 0) { tq[j] = tj; ts[j] = tj; }
         __syncthreads();                      // (red and column j are read no more)
     }
     for (int c = wv; c < n; c += 4)
         for (int i = lane; i < m; i += 64) Fq[(size_t) c * ldf + i] = As[c * ld + i];
-    if (t == 0) {
-        int inf = 0;
-        for (int i = n - 1; i >= 0; --i)
-            if (As[i * ld + i] == 0.0) inf = i + 1;
-        *sinfo = inf;
-        info[q] = inf;
-    }
+    if (t == 0) info[q] = *sinfo = qb_info_serial(As, ld, n);
     __syncthreads();
     if (*sinfo) return;                       // (all or nothing: B is as it was)
-    if (t < nrhs) {                           // (nrhs < 64: one thread per right-hand side) R^T y = b, l ascending; R(l, k) = As[k * ld + l]
-        double* xr = As + (size_t) (n + t) * ld;
-        for (int k = 0; k < n; ++k) {
-            double s = xr[k];
-            for (int l = 0; l < k; ++l) s = fma(-As[k * ld + l], xr[l], s);
-            xr[k] = s / As[k * ld + k];
-        }
-    }
+    if (t < nrhs) qb_trsv_t(As, ld, n, As + (size_t) (n + t) * ld);           // (nrhs < 64: one thread per right-hand side) R^T y = b
     __syncthreads();
     // wave wv: right-hand sides wv, wv + 4, ..: the reflectors n-1 .. 0 on [y ; 0], each a wave-strided dot product and a butterfly
     for (int c = n + wv; c < ntot; c += 4) {
@@ -256,14 +158,8 @@ __global__ void __launch_bounds__(256) bm_wg_kernel(int tr, const double* A, int
         for (int j = n - 1; j >= 0; --j) {
             const double tj = ts[j];
             if (tj == 0.0) continue;          // (H = I; wave-uniform)
-            const double* vj = As + j * ld;
-            double d = 0.0;
-            for (int i = j + 1 + lane; i < m; i += 64) d = fma(vj[i], bc[i], d);
-            d = bm_wave_sum(d);
-            const double tw = tj * (bc[j] + d);
-            for (int i = j + 1 + lane; i < m; i += 64) bc[i] = fma(-tw, vj[i], bc[i]);
-            if (lane == 0) bc[j] -= tw;
-            BM_WAVE_SYNC();                   // (the next reflector reads the column under another lane map)
+            qb_col_reflect(As + j * ld, bc, j, m, tj, lane);
+            QB_WAVE_SYNC();                   // (the next reflector reads the column under another lane map)
         }
         double* dst = Bq + (size_t) (c - n) * ldb;
         for (int i = lane; i < m; i += 64) dst[i] = bc[i];
@@ -280,7 +176,7 @@ __global__ void __launch_bounds__(256) bm_wg_kernel(int tr, const double* A, int
 #define BM_ROWREGS 8
 static_assert(QRD_B_MAX_ROWS <= 64 * BM_ROWREGS, "a right-hand side is held in BM_ROWREGS registers per lane");
 
-__host__ __device__ __forceinline__ size_t bm_apply_lds(int m, int n) { return sizeof(double) * ((size_t) n * bm_ld(m) + BM_MAXN); }
+__host__ __device__ __forceinline__ size_t bm_apply_lds(int m, int n) { return sizeof(double) * ((size_t) n * qb_ld(m) + BM_MAXN); }
 
 template <int RR>
 __global__ void __launch_bounds__(256) bm_apply_kernel(const double* __restrict__ A, int m, int n, int lda, size_t strideA,
@@ -290,7 +186,7 @@ __global__ void __launch_bounds__(256) bm_apply_kernel(const double* __restrict_
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const size_t q = blockIdx.x;
-    const int ld = bm_ld(m);
+    const int ld = qb_ld(m);
     double* Vs = sm;
     double* ts = Vs + (size_t) n * ld;
     const double* Aq = A + q * strideA;
@@ -299,16 +195,14 @@ __global__ void __launch_bounds__(256) bm_apply_kernel(const double* __restrict_
         for (int i = lane; i < m; i += 64) Vs[c * ld + i] = Aq[(size_t) c * lda + i];
     if (t < n) ts[t] = tau[q * stridetau + t];
     __syncthreads();
-    const double dg = lane < n ? Vs[lane * ld + lane] : 1.0;
-    const unsigned long long z = __ballot(lane < n && dg == 0.0);
-    const int inf = z ? __ffsll((long long) z) : 0;           // (the same value in every wave of every workgroup of the member)
+    const int inf = qb_info_wave(lane < n ? Vs[lane * ld + lane] : 1.0, n, lane);    // (the same value in every wave of every workgroup of the member)
     if (blockIdx.y == 0 && t == 0) info[q] = inf;
     if (inf) return;
     for (int col = (int) blockIdx.y * 4 + wv; col < nrhs; col += (int) gridDim.y * 4) {       // (wave-uniform)
         double* cp = Bq + (size_t) col * ldb;
         double b = lane < n ? cp[lane] : 0.0;
         for (int k = 0; k < n; ++k) {
-            const double yk = bm_bcast(b, k) / Vs[k * ld + k];
+            const double yk = qb_bcast(b, k) / Vs[k * ld + k];
             if (lane == k) b = yk;
             else if (lane > k && lane < n) b = fma(-Vs[lane * ld + k], yk, b);
         }
@@ -319,18 +213,7 @@ __global__ void __launch_bounds__(256) bm_apply_kernel(const double* __restrict_
         for (int j = n - 1; j >= 0; --j) {
             const double tj = ts[j];
             if (tj == 0.0) continue;          // (H = I; wave-uniform)
-            const double* vj = Vs + j * ld;
-            double v[RR];
-            double d = 0.0;
-#pragma unroll
-            for (int r = 0; r < RR; ++r) {
-                const int i = lane + 64 * r;
-                v[r] = (i > j && i < m) ? vj[i] : (i == j ? 1.0 : 0.0);
-                d = fma(v[r], c[r], d);
-            }
-            const double tw = tj * bm_wave_sum(d);
-#pragma unroll
-            for (int r = 0; r < RR; ++r) c[r] = fma(-tw, v[r], c[r]);
+            qb_regs_reflect<RR>(Vs + j * ld, j, m, tj, c, lane);
         }
 #pragma unroll
         for (int r = 0; r < RR; ++r) {
@@ -365,27 +248,18 @@ __global__ void __launch_bounds__(256) bm_transpose_kernel(const double* __restr
     }
 }
 
-// more than 64 KiB of LDS per workgroup has to be allowed per kernel and device, once
+// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
 static int bm_allow_lds(void)
 {
     static std::atomic<int> done[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int) e;
-    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
-    const void* fns[] = {reinterpret_cast<const void*>(bm_wg_kernel),
-                         reinterpret_cast<const void*>(bm_apply_kernel<1>),
-                         reinterpret_cast<const void*>(bm_apply_kernel<2>),
-                         reinterpret_cast<const void*>(bm_apply_kernel<4>),
-                         reinterpret_cast<const void*>(bm_apply_kernel<8>),
-                         reinterpret_cast<const void*>(bm_wave_kernel<32, false>),
-                         reinterpret_cast<const void*>(bm_wave_kernel<32, true>)};
-    for (const void* f : fns) {
-        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, BM_LDS_CAP);
-        if (e != hipSuccess) return (int) e;
-    }
-    if (dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
-    return 0;
+    const void* const fns[] = {reinterpret_cast<const void*>(bm_wg_kernel),
+                               reinterpret_cast<const void*>(bm_apply_kernel<1>),
+                               reinterpret_cast<const void*>(bm_apply_kernel<2>),
+                               reinterpret_cast<const void*>(bm_apply_kernel<4>),
+                               reinterpret_cast<const void*>(bm_apply_kernel<8>),
+                               reinterpret_cast<const void*>(bm_wave_kernel<32, false>),
+                               reinterpret_cast<const void*>(bm_wave_kernel<32, true>)};
+    return qb_allow_lds(fns, done);
 }
 
 template <int W>

@@ -27,29 +27,14 @@
 // group): results are bitwise repeatable, independent of `batch` and of a matrix's index, and sigma does not depend on whether W is
 // accumulated.  No atomics, nothing crosses a workgroup, nothing spins.
 //
+// From qr_batched_dev.h: the wave helpers, the dlarfg scalars (bs_house) and the LDS opt-in.
+//
 // Out of scope: a single launch fused with the factorisation and with the product by Q; wide matrices; n > 64.
-#include <atomic>
 #include <float.h>
 
-#include "qr_common.h"
-#include "qr_device.h"
+#include "qr_batched_dev.h"
 
 static_assert(QRD_B_MAX_N == 64, "a column per lane of one wave: at most 64 columns");
-
-#define BS_WAVE_SYNC()                                           \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
-        __builtin_amdgcn_wave_barrier();                         \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
-    } while (0)
-
-// the same sum in every lane; the order of the additions does not depend on the data
-__device__ __forceinline__ double bs_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // leading dimension of G and W: >= n, 4 mod 8 for n <= 32 and 8 mod 16 above (see the header of this file)
 __host__ __device__ __forceinline__ int bs_ld(int n) { return n <= 32 ? ((n + 3) / 8) * 8 + 4 : ((n + 7) / 16) * 16 + 8; }
@@ -63,23 +48,22 @@ __device__ __forceinline__ void bs_house(double* Gs, int ld, int n, int r, doubl
     const bool in = lane < n;
     for (int j = 0; j < r; ++j) {
         const double x = in && lane > j ? Gs[j * ld + lane] : 0.0;
-        const double ssq = bs_wave_sum(x * x);
+        const double ssq = qb_wave_sum(x * x);
         const double alpha = Gs[j * ld + j];
         double tj = 0.0;
         if (ssq != 0.0) {                     // (wave-uniform)
-            const double beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
-            const double scal = 1.0 / (alpha - beta);
-            tj = (beta - alpha) / beta;
+            double beta, scal;                // (beta is not stored: only the trailing columns of this Q are used)
+            tj = qb_larfg(alpha, ssq, beta, scal);
             const double v = lane > j ? x * scal : (lane == j ? 1.0 : 0.0);
             for (int c = j + 1; c < r; ++c) {
                 const double y = in && lane >= j ? Gs[c * ld + lane] : 0.0;
-                const double w = tj * bs_wave_sum(v * y);
+                const double w = tj * qb_wave_sum(v * y);
                 if (in && lane >= j) Gs[c * ld + lane] = fma(-w, v, y);
             }
             if (in && lane > j) Gs[j * ld + lane] = v;
         }
         if (lane == 0) taus[j] = tj;
-        BS_WAVE_SYNC();                       // (the next column's alpha was written by another lane)
+        QB_WAVE_SYNC();                       // (the next column's alpha was written by another lane)
     }
 }
 
@@ -98,7 +82,7 @@ __global__ void __launch_bounds__(256) bs_jsvd_kernel(const double* __restrict__
     const int t = WG ? (int) threadIdx.x : lane;
     const size_t q = WG ? (size_t) blockIdx.x : (size_t) blockIdx.x * 4 + wv;
     if (!WG && q >= (size_t) batch) return;   // (wave route: no workgroup barrier below, the waves are independent)
-#define BS_SYNC() do { if (WG) __syncthreads(); else BS_WAVE_SYNC(); } while (0)
+#define BS_SYNC() do { if (WG) __syncthreads(); else QB_WAVE_SYNC(); } while (0)
     const bool wantu = U != nullptr;
     const int ld = bs_ld(n);
     double* Gs = sm + (WG ? 0 : (size_t) wv * bs_doubles(n, wantu));
@@ -260,7 +244,7 @@ __global__ void __launch_bounds__(256) bs_jsvd_kernel(const double* __restrict__
         double y = lane == k ? 1.0 : 0.0;
         for (int j = r - 1; j >= 0; --j) {
             const double v = lane < n && lane > j ? Gs[j * ld + lane] : (lane == j ? 1.0 : 0.0);
-            const double w = taus[j] * bs_wave_sum(v * y);
+            const double w = taus[j] * qb_wave_sum(v * y);
             y = fma(-w, v, y);
         }
         if (lane < n) Vq[(size_t) k * ldv + row] = y;
@@ -268,20 +252,12 @@ __global__ void __launch_bounds__(256) bs_jsvd_kernel(const double* __restrict__
 #undef BS_SYNC
 }
 
-// more than 64 KiB of LDS per workgroup has to be allowed per kernel and device, once
+// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
 static int bs_allow_lds(void)
 {
     static std::atomic<int> done[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int) e;
-    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
-    const int cap = 160 * 1024;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(bs_jsvd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bs_jsvd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess && dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
-    return (int) e;
+    const void* const fns[] = {reinterpret_cast<const void*>(bs_jsvd_kernel<false>), reinterpret_cast<const void*>(bs_jsvd_kernel<true>)};
+    return qb_allow_lds(fns, done);
 }
 
 extern "C" {

@@ -26,42 +26,24 @@
 //
 // Every sum runs in a fixed order that (n, nrhs, p_add, p_del) alone fix (wave butterflies, waves added in wave order, serial loops):
 // repeated launches are bitwise equal and a member's result does not depend on the batch count or its index.  No atomics.
-#include <atomic>
-
-#include "qr_common.h"
-#include "qr_device.h"
+//
+// From qr_batched_dev.h: the wave helpers, the leading dimension and the LDS opt-in.  The column step and its scalars are this file's
+// own: the signed sums and bu_hypot are another formula than dlarfg's, on purpose.
+#include "qr_batched_dev.h"
 
 #define BU_MAXN QRD_B_MAX_N
 #define BU_P QRD_BU_MAXROWS              // one block row per thread
 #define BU_P_WIDE QRD_BU_MAXROWS_WIDE    // what 33 .. 64 columns leave
-#define BU_LDS_CAP (160 * 1024)
 
-// the same sum in every lane; the order of the additions does not depend on the data (b_wave_sum of qr_batched.hip)
-__device__ __forceinline__ double bu_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// the smallest leading dimension >= p that is 2 mod 32 (b_ld of qr_batched.hip)
-__host__ __device__ constexpr int bu_ld(int p) { return ((p + 29) / 32) * 32 + 2; }
-// the triangle's: the smallest odd value >= n
+// the block image is at qb_ld(p); the triangle's leading dimension: the smallest odd value >= n
 __host__ __device__ constexpr int bu_lr(int n) { return n | 1; }
 // doubles of LDS of the workgroup route: the two images, tau[64], red[8]
-__host__ __device__ constexpr size_t bu_wg_doubles(int n, int ntot, int p) { return (size_t) ntot * (bu_ld(p) + bu_lr(n)) + BU_MAXN + 8; }
+__host__ __device__ constexpr size_t bu_wg_doubles(int n, int ntot, int p) { return (size_t) ntot * (qb_ld(p) + bu_lr(n)) + BU_MAXN + 8; }
 
 static_assert(QRD_B_MAX_N == 64 && BU_P == 256, "at most 64 columns, one block row per thread of a 256-thread workgroup");
-static_assert(sizeof(double) * bu_wg_doubles(32, 32, BU_P) <= BU_LDS_CAP, "256 rows fit beside 32 columns");
-static_assert(sizeof(double) * bu_wg_doubles(64, 64, BU_P_WIDE) <= BU_LDS_CAP, "BU_P_WIDE rows fit beside the unpacked 64 x 65 triangle");
-static_assert(sizeof(double) * bu_wg_doubles(64, 64, BU_P_WIDE + 1) > BU_LDS_CAP, "and no row more: the next leading dimension is 258");
-
-// v of lane l, l wave-uniform
-__device__ __forceinline__ double bu_bcast(double v, int l)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
+static_assert(sizeof(double) * bu_wg_doubles(32, 32, BU_P) <= QB_LDS_CAP, "256 rows fit beside 32 columns");
+static_assert(sizeof(double) * bu_wg_doubles(64, 64, BU_P_WIDE) <= QB_LDS_CAP, "BU_P_WIDE rows fit beside the unpacked 64 x 65 triangle");
+static_assert(sizeof(double) * bu_wg_doubles(64, 64, BU_P_WIDE + 1) > QB_LDS_CAP, "and no row more: the next leading dimension is 258");
 
 // hypot(x, y) with the sum of squares carried in two doubles and rounded once (error just above half an ulp).  The library function is
 // good to an ulp -- on an MI355X it was one ulp off the nearest double on 3 of 9 Gaussian pairs -- which is more than the Gram bound
@@ -129,9 +111,9 @@ __global__ void __launch_bounds__(256) bu_wave_kernel(const qrd_bu_args a)
     for (int j = 0; j < W; ++j) {
         if (j < n) {                          // (wave-uniform)
             const double x = b[j], x2 = x * x;                   // (rows >= p hold zeros)
-            const double sa = bu_wave_sum(neg ? 0.0 : x2), sd = bu_wave_sum(neg ? x2 : 0.0);
+            const double sa = qb_wave_sum(neg ? 0.0 : x2), sd = qb_wave_sum(neg ? x2 : 0.0);
             if (sa != 0.0 || sd != 0.0) {     // (the same values in every lane)
-                const double alpha = bu_bcast(r[j], j);
+                const double alpha = qb_bcast(r[j], j);
                 const double h = bu_hypot(alpha, sqrt(sa)), nd = sqrt(sd), d = (h - nd) * (h + nd);
                 if (!(d > 0.0) || !isfinite(d)) {
                     if (lane == 0 && a.info) a.info[q] = j + 1;
@@ -143,7 +125,7 @@ __global__ void __launch_bounds__(256) bu_wave_kernel(const qrd_bu_args a)
 #pragma unroll
                 for (int c = j + 1; c < W; ++c) {
                     if (c < ntot) {
-                        const double tw = tj * (bu_bcast(r[c], j) + bu_wave_sum(sv * b[c]));
+                        const double tw = tj * (qb_bcast(r[c], j) + qb_wave_sum(sv * b[c]));
                         if (lane == j) r[c] -= tw;
                         b[c] = fma(-tw, v, b[c]);
                     }
@@ -171,7 +153,7 @@ __global__ void __launch_bounds__(256) bu_wave_kernel(const qrd_bu_args a)
         for (int c = 0; c < W; ++c) {
             if (c >= n && c < ntot) {
                 const double e2 = b[c] * b[c];
-                const double ea = bu_wave_sum(neg ? 0.0 : e2), ed = bu_wave_sum(neg ? e2 : 0.0);
+                const double ea = qb_wave_sum(neg ? 0.0 : e2), ed = qb_wave_sum(neg ? e2 : 0.0);
                 double* s = a.rss + q * (size_t) a.nrhs + (c - n);
                 if (lane == 0) *s = fmax(0.0, (*s + ea) - ed);
             }
@@ -187,7 +169,7 @@ __global__ void __launch_bounds__(256) bu_wave_kernel(const qrd_bu_args a)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// workgroup route.  LDS: Bs[c * ld + i] = [B | C2](i, c), ld = bu_ld(p); Rs[c * lr + r] = [R | Z](r, c), lr = bu_lr(n); ts[64]; red[8].
+// workgroup route.  LDS: Bs[c * ld + i] = [B | C2](i, c), ld = qb_ld(p); Rs[c * lr + r] = [R | Z](r, c), lr = bu_lr(n); ts[64]; red[8].
 // ---------------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) bu_wg_kernel(const qrd_bu_args a)
 {
@@ -195,7 +177,7 @@ __global__ void __launch_bounds__(256) bu_wg_kernel(const qrd_bu_args a)
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const size_t q = blockIdx.x;
     const int n = a.n, ntot = a.n + a.nrhs, p = a.p, p_add = a.p_add;
-    const int ld = bu_ld(p), lr = bu_lr(n);
+    const int ld = qb_ld(p), lr = bu_lr(n);
     int held = 0;
     if (a.acc) {
         held = a.rows[q];
@@ -224,7 +206,7 @@ __global__ void __launch_bounds__(256) bu_wg_kernel(const qrd_bu_args a)
         double* vj = Bs + j * ld;
         // thread t owns row t (p <= 256): its square goes to the sum of its sign
         const double x = t < p ? vj[t] : 0.0, x2 = x * x;
-        const double sa_w = bu_wave_sum(t < p_add ? x2 : 0.0), sd_w = bu_wave_sum(t < p_add ? 0.0 : x2);
+        const double sa_w = qb_wave_sum(t < p_add ? x2 : 0.0), sd_w = qb_wave_sum(t < p_add ? 0.0 : x2);
         if (lane == 0) { red[wv] = sa_w; red[4 + wv] = sd_w; }
         __syncthreads();
         const double sa = ((red[0] + red[1]) + red[2]) + red[3], sd = ((red[4] + red[5]) + red[6]) + red[7];
@@ -250,7 +232,7 @@ __global__ void __launch_bounds__(256) bu_wg_kernel(const qrd_bu_args a)
                 double* bc = Bs + c * ld;
                 double dt = 0.0;
                 for (int i = lane; i < p; i += 64) dt = fma(i < p_add ? vj[i] : -vj[i], bc[i], dt);
-                dt = bu_wave_sum(dt);
+                dt = qb_wave_sum(dt);
                 const double tw = tau * (Rs[c * lr + j] + dt);
                 for (int i = lane; i < p; i += 64) bc[i] = fma(-tw, vj[i], bc[i]);
                 if (lane == 0) Rs[c * lr + j] -= tw;     // (read by every lane above: the wave runs in lock step up to the butterfly)
@@ -276,8 +258,8 @@ __global__ void __launch_bounds__(256) bu_wg_kernel(const qrd_bu_args a)
                 if (i < p_add) ea += e2;
                 else ed += e2;
             }
-            ea = bu_wave_sum(ea);
-            ed = bu_wave_sum(ed);
+            ea = qb_wave_sum(ea);
+            ed = qb_wave_sum(ed);
             double* s = a.rss + q * (size_t) a.nrhs + (c - n);
             if (lane == 0) *s = fmax(0.0, (*s + ea) - ed);
         }
@@ -295,8 +277,8 @@ __global__ void __launch_bounds__(256) bu_wg_kernel(const qrd_bu_args a)
 // its inverse H_0 .. H_{n-1} (tr == 0).  LDS: Vs[c * ld + i] = V(i, c), then tau[64].  A wave takes a column: lane j < n holds C1(j), row
 // lane + 64 k of C2 is in register k -- RR = 1, 2 or 4, the smallest that holds p rows.  (A register beyond p adds exact zeros.)
 // ---------------------------------------------------------------------------------------------------------------------------------
-__host__ __device__ constexpr size_t bu_apply_doubles(int n, int p) { return (size_t) n * bu_ld(p) + BU_MAXN; }
-static_assert(sizeof(double) * bu_apply_doubles(32, BU_P) <= BU_LDS_CAP && sizeof(double) * bu_apply_doubles(64, BU_P_WIDE) <= BU_LDS_CAP,
+__host__ __device__ constexpr size_t bu_apply_doubles(int n, int p) { return (size_t) n * qb_ld(p) + BU_MAXN; }
+static_assert(sizeof(double) * bu_apply_doubles(32, BU_P) <= QB_LDS_CAP && sizeof(double) * bu_apply_doubles(64, BU_P_WIDE) <= QB_LDS_CAP,
               "V fits wherever the update that wrote it did");
 
 template <int RR>
@@ -307,7 +289,7 @@ __global__ void __launch_bounds__(256) bu_apply_kernel(int tr, const double* __r
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const size_t q = blockIdx.x;
-    const int ld = bu_ld(p);
+    const int ld = qb_ld(p);
     double* Vs = sm;
     double* ts = Vs + (size_t) n * ld;
     const double* Vq = V + q * strideV;
@@ -338,7 +320,7 @@ __global__ void __launch_bounds__(256) bu_apply_kernel(int tr, const double* __r
                 v[k] = i < p ? vj[i] : 0.0;
                 d = fma(i < p_add ? v[k] : -v[k], c[k], d);
             }
-            const double tw = tj * (bu_bcast(c1, j) + bu_wave_sum(d));
+            const double tw = tj * (qb_bcast(c1, j) + qb_wave_sum(d));
             if (lane == j) c1 -= tw;
 #pragma unroll
             for (int k = 0; k < RR; ++k) c[k] = fma(-tw, v[k], c[k]);
@@ -368,23 +350,13 @@ __global__ void __launch_bounds__(256) bu_solve_prep_kernel(const double* __rest
         for (int c = threadIdx.x; c < nrhs; c += 256) resid[q * strideresid + c] = sqrt(rss[q * (size_t) nrhs + c]);
 }
 
-// more than 64 KiB of LDS per workgroup has to be allowed per kernel and device, once
+// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
 static int bu_allow_lds(void)
 {
     static std::atomic<int> done[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int) e;
-    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(bu_wg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BU_LDS_CAP);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bu_apply_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, BU_LDS_CAP);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bu_apply_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, BU_LDS_CAP);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(bu_apply_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, BU_LDS_CAP);
-    if (e == hipSuccess && dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
-    return (int) e;
+    const void* const fns[] = {reinterpret_cast<const void*>(bu_wg_kernel), reinterpret_cast<const void*>(bu_apply_kernel<1>),
+                               reinterpret_cast<const void*>(bu_apply_kernel<2>), reinterpret_cast<const void*>(bu_apply_kernel<4>)};
+    return qb_allow_lds(fns, done);
 }
 
 extern "C" {

@@ -896,7 +896,7 @@ int qr_lstsq_rolling_batched(const double* A, int m, int n, const double* B, int
  *
  * Routes.  The fused calls hold the right-hand sides beside the matrix as nrhs more columns of height rows: one wave per member (four
  * members per workgroup) for rows <= 64 and cols + nrhs <= 32, otherwise one workgroup per member with [F | X] in LDS.  The
- * factorisation step is section 8's, operation for operation, and does not touch the right-hand sides: dA / dtau of
+ * factorisation step is section 8's, the same code, and does not touch the right-hand sides: dA / dtau of
  * qr_gels_t_batched_dev and dF / dtau of qr_gels_wide_batched_dev are bitwise those of qr_geqrf_batched_dev (on the same matrix, on the
  * explicit transpose) whenever (rows, cols) and (rows, cols + nrhs) take the same route, and always on the composed routes.  Then
  * R^T y = b by forward substitution, y_k = (b_k - sum_{l<k} R(l,k) y_l) / R(k,k) with l ascending, and X = H_0 .. H_{cols-1} [y ; 0]

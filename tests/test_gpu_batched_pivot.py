@@ -481,6 +481,32 @@ def test_unpivoted_factorisation_is_unchanged_by_a_pivoted_call_on_the_plan(qr, 
     assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
 
 
+# (5, 3), (16, 4): geqp3 takes the 4-register wave kernel, geqrf the 8-register one; (64, 28): 32 registers; (65, 8): the first row count
+# of the workgroup route
+PERMUTED = [(5, 3), (16, 4), (64, 28), (65, 8), (100, 33), (256, 64)]
+
+
+@pytest.mark.parametrize("m,n", PERMUTED)
+def test_factors_equal_geqrf_on_permuted_columns_bitwise(qr, plan, m, n):
+    """The pivoted kernels run the unpivoted kernels' column step: geqrf on A[:, jpvt] returns geqp3's factors and tau bit for bit."""
+    batch = 5                                              # (a partly filled workgroup on the wave route)
+    rng = np.random.default_rng(7000 * m + n)
+    A = rng.standard_normal((batch, m, n)) * 2.0 ** rng.uniform(-3.0, 3.0, (batch, 1, n))
+    for q in range(batch):                                 # the largest column is not the first: step 0 swaps in every member
+        if np.argmax(np.linalg.norm(A[q], axis=0)) == 0:
+            A[q][:, [0, 1]] = A[q][:, [1, 0]]
+    F, tau, jp, _ = _geqp3(plan, A, with_q=False)
+    assert np.all(np.sort(jp, axis=1) == np.arange(n))
+    assert not np.any(np.all(jp == np.arange(n), axis=1)), "a member was not permuted: the comparison would be vacuous"
+    AP = np.take_along_axis(A, jp[:, None, :], axis=2)
+    dA, dtau = _up(_pack(AP)), _up(np.full((batch, n), SENTINEL))
+    plan.geqrf_batched(dA, m, n, m, m * n, dtau, n, batch)
+    plan.sync()
+    F0, tau0 = _down(dA).transpose(0, 2, 1), _down(dtau)
+    print(f"geqp3 against geqrf on the permuted columns {m}x{n}: {int(np.sum(F != F0))} factor entries and {int(np.sum(tau != tau0))} tau differ")
+    assert np.array_equal(F, F0) and np.array_equal(tau, tau0)
+
+
 def test_host_twins_and_python_wrappers(qr):
     m, n, nrhs = 20, 6, 3
     A, Bm, ranks = _rank_batch(m, n, 4, nrhs)
