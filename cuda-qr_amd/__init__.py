@@ -195,6 +195,14 @@ _sig("qr_transpose_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _
 _sig("qr_gels_wide_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, _vp,
      C.c_int)
 _sig("qr_lstsq_minnorm_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip)
+_sig("qr_damped_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, C.c_int, _ll, _vp, _vp, _ll, _vp, _ll, _vp, C.c_int, _ll,
+     C.c_int, _vp, C.c_int, _ll, _vp, _vp, _vp, C.c_int)
+_sig("qr_gels_damped_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int,
+     _ll, _vp, C.c_int, _ll, _vp, _vp, _vp, C.c_int)
+_sig("qr_gels_damped_wide_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, _ll,
+     _vp, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _vp, _vp, C.c_int)
+_sig("qr_lsacc_batched_solve_damped_dev", C.c_int, _vp, _vp, _ll, _vp, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _vp, _vp)
+_sig("qr_lstsq_damped_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -650,6 +658,43 @@ def lstsq_minnorm_batched(A, B):
     return X.transpose(0, 2, 1), info[:batch].astype(np.int64)
 
 
+def lstsq_damped_batched(A, B, lam, D=None):
+    """min ||A_q x - b||^2 + lam^2 ||D_q x||^2 for every member of A (batch, m, n), B (batch, m, nrhs) and every lam of a list, through
+    qr_lstsq_damped_batched.  lam: (nlam,) shared by every member, or (batch, nlam); D: None (the identity), (n,) or (batch, n); a wide
+    A (m < n) requires D is None.  Returns (X, xnorm, resid, info): X (batch, nlam, n, nrhs), xnorm = ||D x|| and resid = ||A x - b||
+    (batch, nlam, nrhs), info (batch, nlam) = 0, or i + 1 for the smallest i with a zero on the damped triangle's diagonal (that X
+    holds no solution; the others are solved).  A singular pair does not raise."""
+    At = _packed_batch(A, "lstsq_damped_batched")
+    Bt = _packed_batch(B, "lstsq_damped_batched")
+    batch, n, m = At.shape
+    if Bt.shape[0] != batch or Bt.shape[2] != m:
+        raise QRError(f"lstsq_damped_batched: B is {Bt.shape[0]} matrices of {Bt.shape[2]} rows, A is {batch} of {m}", QR_E_ARG)
+    nrhs = Bt.shape[1]
+    lam = np.asarray(lam, dtype=np.float64)
+    if lam.ndim == 1:
+        lam = np.broadcast_to(lam, (batch, lam.shape[0]))
+    if lam.ndim != 2 or lam.shape[0] != batch or lam.shape[1] < 1:
+        raise QRError(f"lstsq_damped_batched: lam must be (nlam,) or ({batch}, nlam) with nlam >= 1, got {lam.shape}", QR_E_ARG)
+    lam = np.ascontiguousarray(lam)
+    nlam = lam.shape[1]
+    if D is not None:
+        D = np.asarray(D, dtype=np.float64)
+        if D.ndim == 1:
+            D = np.broadcast_to(D, (batch, D.shape[0]))
+        if D.shape != (batch, n):
+            raise QRError(f"lstsq_damped_batched: D must be ({n},) or ({batch}, {n}), got {D.shape}", QR_E_ARG)
+        D = np.ascontiguousarray(D)
+    X = np.empty((batch, nlam, nrhs, n))
+    xnorm = np.empty((batch, nlam, nrhs))
+    resid = np.empty((batch, nlam, nrhs))
+    info = np.zeros((max(batch, 1), nlam), dtype=np.intc)
+    rc = lib.qr_lstsq_damped_batched(_p(At), m, n, _p(Bt), nrhs, batch, None if D is None else _p(D), _p(lam), nlam, _p(X), _p(xnorm),
+                                     _p(resid), info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_damped_batched")
+    return X.transpose(0, 1, 3, 2), xnorm, resid, info[:batch].astype(np.int64)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -966,6 +1011,30 @@ class Plan:
         check(lib.qr_gels_wide_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dF), ldf, strideF, _dptr(dtau), stridetau, _dptr(dB),
                                            nrhs, ldb, strideB, _dptr(dinfo), batch), "qr_gels_wide_batched_dev")
 
+    def damped_batched(self, dR, n, ldr, strideR, dZ, nrhs, ldz, strideZ, dlam, nlam, stridelam, dX, ldx, strideX, dinfo, batch, drss=None,
+                       djpvt=None, stridejpvt=0, dD=None, strideD=0, flip=False, dxnorm=None, dresid=None):
+        """the damped solves min ||A x - b||^2 + lam_k^2 ||D x||^2 of `batch` members from factors that exist: dR (n x n, upper triangle),
+        dZ (n x nrhs, the top of Q^T B), drss (tail sums of squares), djpvt (the factors are geqp3_batched's), flip (the triangle is the
+        reversed transpose of R: the wide case).  dX: n x (nlam * nrhs) per member; dinfo: nlam ints per member"""
+        check(lib.qr_damped_batched_dev(self.h, _dptr(dR), n, ldr, strideR, _dptr(dZ), nrhs, ldz, strideZ, _dptr(drss), _dptr(djpvt), stridejpvt,
+                                        _dptr(dD), strideD, _dptr(dlam), nlam, stridelam, int(bool(flip)), _dptr(dX), ldx, strideX, _dptr(dxnorm),
+                                        _dptr(dresid), _dptr(dinfo), batch), "qr_damped_batched_dev")
+
+    def gels_damped_batched(self, dA, m, n, lda, strideA, dtau, stridetau, dB, nrhs, ldb, strideB, dlam, nlam, stridelam, dX, ldx, strideX, dinfo,
+                            batch, dD=None, strideD=0, dxnorm=None, dresid=None):
+        """m >= n: dA factored in place (as geqrf_batched leaves it), dB <- Q^T B in all rows, the damped solutions of every lam to dX"""
+        check(lib.qr_gels_damped_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, _dptr(dB), nrhs, ldb, strideB,
+                                             _dptr(dD), strideD, _dptr(dlam), nlam, stridelam, _dptr(dX), ldx, strideX, _dptr(dxnorm),
+                                             _dptr(dresid), _dptr(dinfo), batch), "qr_gels_damped_batched_dev")
+
+    def gels_damped_wide_batched(self, dA, m, n, lda, strideA, dF, ldf, strideF, dtau, stridetau, dB, nrhs, ldb, strideB, dlam, nlam, stridelam,
+                                 dX, ldx, strideX, dinfo, batch, dxnorm=None, dresid=None):
+        """m < n, D = I: dA untouched, the factors of A^T to dF and dtau, dB (m x nrhs) read only, the damped solutions (n x (nlam * nrhs))
+        to dX"""
+        check(lib.qr_gels_damped_wide_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dF), ldf, strideF, _dptr(dtau), stridetau,
+                                                  _dptr(dB), nrhs, ldb, strideB, _dptr(dlam), nlam, stridelam, _dptr(dX), ldx, strideX,
+                                                  _dptr(dxnorm), _dptr(dresid), _dptr(dinfo), batch), "qr_gels_damped_wide_batched_dev")
+
     def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
         """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""
         check(lib.qr_geqrf_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, batch), "qr_geqrf_batched_dev")
@@ -1228,6 +1297,11 @@ class LsAccumulatorBatched:
         dinfo: 0 or the first zero pivot + 1"""
         check(lib.qr_lsacc_batched_solve_dev(self.h, _dptr(dX), ldx, strideX, _dptr(dresid), strideresid, _dptr(dinfo)),
               "qr_lsacc_batched_solve_dev")
+
+    def solve_damped(self, dlam, nlam, stridelam, dX, ldx, strideX, dinfo, dD=None, strideD=0, dxnorm=None, dresid=None):
+        """the damped solves of every member from the state, which stays untouched: dX n x (nlam * nrhs) per member, dinfo nlam ints"""
+        check(lib.qr_lsacc_batched_solve_damped_dev(self.h, _dptr(dD), strideD, _dptr(dlam), nlam, stridelam, _dptr(dX), ldx, strideX,
+                                                    _dptr(dxnorm), _dptr(dresid), _dptr(dinfo)), "qr_lsacc_batched_solve_damped_dev")
 
     def reset(self):
         check(lib.qr_lsacc_batched_reset(self.h), "qr_lsacc_batched_reset")

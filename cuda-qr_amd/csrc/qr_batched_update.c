@@ -93,13 +93,8 @@ int qr_tpmqrt_batched_dev(qr_plan* pl, char trans, const double* dV, int p_add, 
                         (size_t) strideC1, dC2, ldc2, (size_t) strideC2, nrhs, batch);
 }
 
-/* ---- the accumulator: per member R (n x n, ld n), Z (n x nrhs, ld n), rss (nrhs), one row count, all on the device ---- */
-struct qr_lsacc_batched {
-    qr_plan* p;
-    int n, nrhs, batch;
-    double *R, *Z, *rss;         /* one allocation */
-    int* rows;
-};
+/* ---- the accumulator: per member R (n x n, ld n), Z (n x nrhs, ld n), rss (nrhs), one row count, all on the device (struct
+ * qr_lsacc_batched: qr_plan_internal.h) ---- */
 
 static size_t acc_doubles(const qr_lsacc_batched* a)
 {

@@ -349,6 +349,34 @@ int qrd_bm_apply(void* stream, const double* A, int m, int n, int lda, size_t st
                  int ldb, size_t strideB, int* info, int batch);
 int qrd_bm_transpose(void* stream, const double* S, int rows, int cols, int lds, size_t strideS, double* D, int ldd, size_t strideD, int batch);
 
+/* batched damped least squares (qr_batched_damped.hip, called from qr_batched_damped.c only -- as above, the stub device layer does not
+ * have them; mi355x_qr.h section 8f).  Per member and per lambda_k, k < nlam: the n rows of lambda_k diag(d) eliminated against the
+ * triangle R with Z riding along, then R~ x = z~.
+ *   R (n x n, ldr >= n; the upper triangle is read), Z (zrows x nrhs, ldz >= zrows >= n: rows 0 .. n-1 are the top of Q^T B, the squares
+ *   of rows n .. zrows-1 are added to rss), rss (nrhs per member, packed; NULL: 0), jpvt (n per member, sj apart; NULL: the identity; S
+ *   uses d[jpvt[j]] in column j and x_j goes to row jpvt[j] of X), D (n per member, sD apart, sD == 0: shared; NULL: ones), lam (nlam per
+ *   member, slam apart, slam == 0: shared).  flip: the triangle is read as U(i, k) = R(n-1-k, n-1-i), Z and the rows of X reversed (D and
+ *   jpvt must be NULL).
+ *   X (xrows x (nlam * nrhs), ldx >= xrows >= n: the solution of (lambda_k, right-hand side r) in column k * nrhs + r, rows n .. xrows-1
+ *   written as zeros), xnorm and resid (nlam * nrhs per member, packed, the same order; either may be NULL), info (nlam per member,
+ *   packed): 0, or i + 1 for the smallest i with R~(i,i) == 0, and then X, xnorm and resid of that pair are not written.
+ * qrd_bd_solve: one launch, a wave per member for n + nrhs <= 32 (qrd_bd_wave_route), else a workgroup per member (n + nrhs <= 64).
+ * qrd_bd_fused: m <= 64 and n + nrhs <= 32 only: qrd_b_geqrf's wave factorisation of [A | B], A, tau and B <- Q^T B (all m rows)
+ * stored, then the same lambda loop on the registers, one launch; B takes the place of Z (ldz >= m, sZ), rss comes from rows n .. m-1;
+ * R, rss, jpvt and flip must be unset, zrows is ignored.  batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_bd_args {
+    const double *R, *Z, *rss, *D, *lam;
+    const int* jpvt;
+    double *X, *xnorm, *resid;
+    int* info;
+    size_t sR, sZ, sj, sD, slam, sX;
+    int ldr, ldz, ldx;
+    int n, nrhs, nlam, zrows, xrows, flip, batch;
+} qrd_bd_args;
+int qrd_bd_wave_route(int ncols);
+int qrd_bd_solve(void* stream, const qrd_bd_args* a);
+int qrd_bd_fused(void* stream, double* A, int m, int lda, size_t strideA, double* tau, size_t stridetau, double* B, const qrd_bd_args* a);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

@@ -108,6 +108,15 @@ struct qr_lsacc {
     double* dd_buf;
 };
 
+/* the batched accumulator (qr_batched_update.c; qr_batched_damped.c solves from it): per member R (n x n, ld n), Z (n x nrhs, ld n), rss
+ * (nrhs) and one row count, all on the device */
+struct qr_lsacc_batched {
+    qr_plan* p;
+    int n, nrhs, batch;
+    double *R, *Z, *rss;         /* one allocation */
+    int* rows;
+};
+
 /* a cached plan of the host-pointer entry points and its device buffers (qr_host.c) */
 typedef struct host_slot {
     int used, busy, cached, dev, m, n, nb;

@@ -47,6 +47,10 @@
  * matrices and one right-hand side each (resident in HBM) go through one qr_gels_wide_batched_dev call: the time, the worst
  * ||A x - b|| / (||A|| ||x||) and the worst distance of x from the row space of A.
  *
+ * `./qr_device m n --batched count --damped nlam` does nothing else either: `count` seeded m x n matrices (m >= n), one right-hand side
+ * and nlam values of lambda each (resident in HBM) go through one qr_gels_damped_batched_dev call: the time, and the worst forward error
+ * ||x - x_s|| / ||x_s|| against nlam qr_gels_batched_dev solves of the stacked systems [A ; lambda I].
+ *
  * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
  * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
  * qr_lsacc_batched_slide_dev for the whole batch -- beside one qr_gels_batched_dev per window on copies of the windows: both wall times
@@ -813,9 +817,103 @@ static int batched_minnorm_main(int m, int n, int count)
     return 0;
 }
 
+/* count matrices of m x n and nlam values of lambda each through one fused damped call, beside nlam stacked plain solves */
+static int batched_damped_main(int m, int n, int count, int nlam)
+{
+    if (n < 1 || n >= QR_BATCHED_MAX_N || m < n || count < 1 || nlam < 1) {
+        fprintf(stderr, "--batched count --damped nlam needs count >= 1, nlam >= 1 and 1 <= n < %d, n <= m\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d matrices of %dx%d, %d lambdas each\n", count, m, n, nlam);
+    const int ms = m + n;
+    const size_t mn = (size_t) m * n, cnt = mn * count, sn = (size_t) ms * n, nx = (size_t) n * nlam;
+    double *A = malloc(sizeof(double) * cnt), *B = malloc(sizeof(double) * (size_t) m * count), *X = malloc(sizeof(double) * nx * count);
+    double *S = malloc(sizeof(double) * sn * count), *C = malloc(sizeof(double) * (size_t) ms * count), *lam = malloc(sizeof(double) * (size_t) nlam);
+    int* info = malloc(sizeof(int) * (size_t) count * nlam);
+    if (!A || !B || !X || !S || !C || !lam || !info) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    for (size_t i = 0; i < (size_t) m * count; i++) B[i] = (double) rand() / RAND_MAX - 0.5;
+    for (int k = 0; k < nlam; k++) lam[k] = 0.05 * sqrt((double) m) * (k + 1);       /* one list for every member: stridelam = 0 */
+    qr_plan* p = NULL;
+    double *dA = NULL, *dB = NULL, *dtau = NULL, *dlam = NULL, *dX = NULL, *dS = NULL, *dC = NULL;
+    int *dinfo = NULL, *dginfo = NULL;
+    if (qr_plan_create(&p, m, n, 0, 0) || qr_device_malloc((void**) &dA, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dB, sizeof(double) * (size_t) m * count) || qr_device_malloc((void**) &dtau, sizeof(double) * (size_t) n * count) ||
+        qr_device_malloc((void**) &dlam, sizeof(double) * (size_t) nlam) || qr_device_malloc((void**) &dX, sizeof(double) * nx * count) ||
+        qr_device_malloc((void**) &dS, sizeof(double) * sn * count) || qr_device_malloc((void**) &dC, sizeof(double) * (size_t) ms * count) ||
+        qr_device_malloc((void**) &dinfo, sizeof(int) * (size_t) count * nlam) || qr_device_malloc((void**) &dginfo, sizeof(int) * (size_t) count) ||
+        qr_copy_to_device(dlam, lam, sizeof(double) * (size_t) nlam)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        if (qr_copy_to_device(dA, A, sizeof(double) * cnt) || qr_copy_to_device(dB, B, sizeof(double) * (size_t) m * count)) {
+            fprintf(stderr, "copy failed\n");
+            return 1;
+        }
+        const double t0 = now();
+        int rc = qr_gels_damped_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dB, 1, m, m, NULL, 0, dlam, nlam, 0, dX, n, (long long) nx, NULL,
+                                            NULL, dinfo, count);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc) {
+            fprintf(stderr, "qr_gels_damped_batched_dev failed: %s%s\n", qr_strerror(rc), rc == QR_E_ARG ? " (the shape does not fit: see qr_batched_max_rows)" : "");
+            return 1;
+        }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(X, dX, sizeof(double) * nx * count) || qr_copy_to_host(info, dinfo, sizeof(int) * (size_t) count * nlam)) {
+        fprintf(stderr, "copy back failed\n");
+        return 1;
+    }
+    int singular = 0, compared = 1;
+    double worst = 0.0, els = 0.0;
+    for (int k = 0; k < nlam && compared; k++) {     /* the route without the damped call: the stacked system, factored again per lambda */
+        memset(S, 0, sizeof(double) * sn * count);
+        memset(C, 0, sizeof(double) * (size_t) ms * count);
+        for (int q = 0; q < count; q++) {
+            for (int c = 0; c < n; c++) {
+                memcpy(S + q * sn + (size_t) c * ms, A + q * mn + (size_t) c * m, sizeof(double) * (size_t) m);
+                S[q * sn + (size_t) c * ms + m + c] = lam[k];
+            }
+            memcpy(C + (size_t) q * ms, B + (size_t) q * m, sizeof(double) * (size_t) m);
+        }
+        if (qr_copy_to_device(dS, S, sizeof(double) * sn * count) || qr_copy_to_device(dC, C, sizeof(double) * (size_t) ms * count)) {
+            fprintf(stderr, "copy failed\n");
+            return 1;
+        }
+        const double t0 = now();
+        int rc = qr_gels_batched_dev(p, dS, ms, n, ms, (long long) sn, dtau, n, dC, 1, ms, ms, dginfo, count);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc == QR_E_ARG) { compared = 0; break; }  /* (m + n rows do not fit: nothing to compare against) */
+        if (rc || qr_copy_to_host(C, dC, sizeof(double) * (size_t) ms * count)) { fprintf(stderr, "qr_gels_batched_dev failed\n"); return 1; }
+        els += now() - t0;
+        for (int q = 0; q < count; q++) {
+            if (info[(size_t) q * nlam + k]) { singular++; continue; }
+            const double *x = X + q * nx + (size_t) k * n, *xs = C + (size_t) q * ms;
+            double nd = 0.0, ns = 0.0;
+            for (int j = 0; j < n; j++) { nd += (x[j] - xs[j]) * (x[j] - xs[j]); ns += xs[j] * xs[j]; }
+            if (ns > 0.0 && sqrt(nd / ns) > worst) worst = sqrt(nd / ns);
+        }
+    }
+    printf(" MMQR ran damped solves of %d %dx%d systems for %d lambdas in %f s (avg over %d)   [batch resident in HBM, one right-hand side each]\n",
+           count, m, n, nlam, el / TRIALS, TRIALS);
+    if (compared)
+        printf(" singular = %d   worst ||x - x_stacked|| / ||x_stacked|| = %.2e   (%d stacked qr_gels_batched_dev solves: %f s, with the copy back)\n",
+               singular, worst, nlam, els);
+    else
+        printf(" the stacked (m + n) x n systems do not fit qr_gels_batched_dev: no comparison\n");
+    qr_device_free(dA); qr_device_free(dB); qr_device_free(dtau); qr_device_free(dlam); qr_device_free(dX); qr_device_free(dS); qr_device_free(dC);
+    qr_device_free(dinfo); qr_device_free(dginfo);
+    qr_plan_destroy(p);
+    free(A); free(B); free(X); free(S); free(C); free(lam); free(info);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -838,6 +936,9 @@ int main(int argc, char** argv)
                 if (strcmp(argv[k], "--svd") == 0) return batched_svd_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--minnorm") == 0) return batched_minnorm_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--damped") == 0)
+                    return batched_damped_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atoi(argv[k + 1]) : 1);
             return batched_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
         }
     for (int i = 3; i < argc; i++)

@@ -949,6 +949,93 @@ int qr_gels_wide_batched_dev(qr_plan* plan, const double* dA, int m, int n, int 
 int qr_lstsq_minnorm_batched(const double* A, int m, int n, const double* B, int nrhs, int batch,
                              double* X, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8f. Batched damped least squares: ridge regression and the Levenberg-Marquardt step.  Per member and per lambda_k of a list of nlam,
+ * min |A x - b|^2 + lambda_k^2 |D x|^2 with D = diag(d) -- damped inverse kinematics, the inner step of per-pixel curve fitting, a ridge
+ * regression tuned over a grid of lambda.  A is factored once; every lambda then costs O(n^3): the n rows of S = lambda D are
+ * eliminated against the n x n triangle R by Householder reflectors with Z = the top of Q^T b riding along (MINPACK qrsolv; LAPACK
+ * dtpqrt with L = n, a triangle stacked on a triangle), and R~ x = z~ is solved.
+ *
+ * Section 8's conventions hold unchanged: member q at base + q * stride, column-major, strides in elements; the plan supplies the
+ * stream only; no call waits on the host; bad arguments return QR_E_ARG before anything touches a device; batch == 0 returns 0 after the
+ * checks and launches nothing; no atomics; every sum in an order that the shape arguments alone fix; results bitwise repeatable and
+ * bitwise independent of `batch`, of a member's index, of nlam and of a lambda's position in its list (every lambda starts from the
+ * untouched factors).  One exception to the stride rule: strideD == 0 and stridelam == 0 are legal and mean one d / one list of lambda
+ * shared by every member; any other value must be at least n / nlam.
+ *
+ * The operands.  dD: n doubles per member, NULL means d = 1.  dlam: nlam >= 1 doubles per member.  Only (lambda d_i)^2 matters to the
+ * mathematics; the signs are the caller's; non-finite values are not detected.
+ *
+ * The step.  With [R | Z] (n x (n + nrhs)) and the block [S | 0], for j = 0 .. n-1, x = S(0..j, j) (row i of the block has its
+ * non-zeros in columns >= i), ssq = |x|^2: ssq == 0 exactly gives tau = 0 and touches nothing; otherwise beta, tau and v are section
+ * 8's dlarfg values of (R(j,j), x), and columns j+1 .. n+nrhs-1 take the reflector [e_j ; v].  R~ overwrites a working copy: the
+ * caller's R and Z are read only.  Then x_k = R~^-1 z~ by the back substitution of section 8.
+ *
+ * Per (member, lambda_k) the calls write: the solution (n x nrhs) into columns k * nrhs .. (k + 1) * nrhs - 1 of dX (ldx >= n, strideX
+ * >= ldx * nlam * nrhs); dxnorm = |D x|_2 and dresid = |A x - b|_2 (nlam * nrhs doubles per member each, packed, in the same order;
+ * either may be NULL), the latter as sqrt(|R x - z|^2 + rss) with R x - z formed from the untouched R and Z and rss the tail sum of
+ * squares of Q^T b; dinfo (nlam ints per member, packed): 0, or i + 1 for the smallest i with R~(i,i) == 0 exactly (lambda = 0 on a
+ * singular R, d_i = 0 on a zero column).  The X, xnorm and resid entries of a failing pair are not written at all; every other pair is
+ * unaffected and the call returns 0.
+ *
+ * Routes.  n + nrhs <= 32: one wave per member, four members per workgroup, lane i holding row i of the factors, of the working copy
+ * and of the block in registers.  Otherwise (n + nrhs <= QR_BATCHED_MAX_N): one workgroup per member with the three images in LDS.
+ *
+ * Out of scope: a trust-region search for lambda on the device (MINPACK lmpar, which finds |D x| ~ Delta by Newton steps; dxnorm is
+ * the value it needs); a general D for wide members; a fused launch on the workgroup route; generalised cross-validation; blocked /
+ * MFMA variants.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The damped solves from factors that exist, one launch.  dR: n x n, ldr >= n, only the upper triangle is read; dZ: n x nrhs, ldz >= n,
+ * the top of Q^T B; drss (may be NULL: 0): nrhs doubles per member, packed, the tail sums of squares.  1 <= n, nrhs >= 1,
+ * n + nrhs <= QR_BATCHED_MAX_N.  djpvt (may be NULL; n ints per member, stridejpvt >= n) passes the factors of qr_geqp3_batched_dev for
+ * A P = Q R: S uses d[jpvt[j]] in column j and the solution is scattered back so that X is in the caller's column order (what MINPACK
+ * lmpar / qrsolv do); an entry outside [0, n) is read as the identity.  flip != 0 reads the triangle as U(i, k) = R(n-1-k, n-1-i) with
+ * Z and the rows of the solution reversed -- the transpose of R made upper triangular, the wide case below; dD and djpvt must then be
+ * NULL. */
+int qr_damped_batched_dev(qr_plan* plan, const double* dR, int n, int ldr, long long strideR,
+                          const double* dZ, int nrhs, int ldz, long long strideZ, const double* drss,
+                          const int* djpvt, long long stridejpvt, const double* dD, long long strideD,
+                          const double* dlam, int nlam, long long stridelam, int flip,
+                          double* dX, int ldx, long long strideX, double* dxnorm, double* dresid, int* dinfo, int batch);
+
+/* m >= n: factor and solve.  dA and dtau come back bitwise as qr_geqrf_batched_dev leaves them; dB (m x nrhs, ldb >= m) comes back as
+ * Q^T B in all rows -- not overwritten by a solution, so qr_damped_batched_dev can damp again later from dA and dB; rss is taken from
+ * rows n .. m-1.  The shape limits are qr_gels_batched_dev's, and n + nrhs <= QR_BATCHED_MAX_N.  ONE launch for m <= 64 and
+ * n + nrhs <= 32 (section 8's wave factorisation of [A | B], then the lambda loop on the registers the factors are in; at lambda = 0
+ * X is bitwise qr_gels_batched_dev's); otherwise qr_geqrf_batched_dev, qr_ormqr_batched_dev 'T' and qr_damped_batched_dev: three. */
+int qr_gels_damped_batched_dev(qr_plan* plan, double* dA, int m, int n, int lda, long long strideA,
+                               double* dtau, long long stridetau,
+                               double* dB, int nrhs, int ldb, long long strideB,
+                               const double* dD, long long strideD, const double* dlam, int nlam, long long stridelam,
+                               double* dX, int ldx, long long strideX, double* dxnorm, double* dresid, int* dinfo, int batch);
+
+/* m < n with D = I (damped inverse kinematics): x = Q [y ; 0] with A^T = Q R and y the minimiser of |R^T y - b|^2 + lambda^2 |y|^2,
+ * which is qr_damped_batched_dev with flip on R.  dA (m x n, lda >= m) is not modified; dF (n x m, ldf >= n) and dtau (m per member)
+ * receive the factors of A^T as in qr_gels_wide_batched_dev; dB (m x nrhs, ldb >= m) is read only; dX is n x (nlam * nrhs), ldx >= n;
+ * dxnorm = |x|, dresid = |A x - b|.  The limits are qr_gels_wide_batched_dev's with m < n, and m + nrhs <= QR_BATCHED_MAX_N.  Four
+ * launches: transpose, geqrf, the damped solves writing [y ; 0], one ormqr 'N' over all nlam * nrhs columns -- which also runs over the
+ * columns of a failing pair: those hold no solution. */
+int qr_gels_damped_wide_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda, long long strideA,
+                                    double* dF, int ldf, long long strideF, double* dtau, long long stridetau,
+                                    const double* dB, int nrhs, int ldb, long long strideB,
+                                    const double* dlam, int nlam, long long stridelam,
+                                    double* dX, int ldx, long long strideX, double* dxnorm, double* dresid, int* dinfo, int batch);
+
+/* qr_damped_batched_dev on the state of a batched accumulator (section 8d): its R, Z and sums, one launch, the state untouched.  A
+ * member that holds fewer than n rows, or none, is solvable for lambda > 0 and gets info 0. */
+int qr_lsacc_batched_solve_damped_dev(qr_lsacc_batched* acc, const double* dD, long long strideD,
+                                      const double* dlam, int nlam, long long stridelam,
+                                      double* dX, int ldx, long long strideX, double* dxnorm, double* dresid, int* dinfo);
+
+/* The damped solves of a packed batch on host pointers (A: m x n, B: m x nrhs per member, both untouched; D: n per member or NULL; lam:
+ * nlam per member): X n x (nlam * nrhs) per member, xnorm and resid (nlam * nrhs per member; may be NULL), info (nlam per member).
+ * m >= n goes the tall route, m < n the wide route, which requires D == NULL.  Returns QR_E_SINGULAR if any info entry is non-zero.
+ * Creates a plan of its own.  Synchronous. */
+int qr_lstsq_damped_batched(const double* A, int m, int n, const double* B, int nrhs, int batch,
+                            const double* D, const double* lam, int nlam,
+                            double* X, double* xnorm, double* resid, int* info);
+
 #ifdef __cplusplus
 }
 #endif
