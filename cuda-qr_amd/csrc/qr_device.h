@@ -24,6 +24,11 @@ int qrd_gemm_tn_update(void* stream, int M, int N, int K, double alpha, const do
                        int ldb, double beta, double* C, int ldc, double* slabs, size_t slab_cap);
 int qrd_gemm_tn_update_wide(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
                             int ldb, double beta, double* C, int ldc, double* slabs, size_t slab_cap);
+/* the same product on the even static K split wherever the shape allows it, nwg workgroups (0: from the stream); kernel tests and A/Bs only */
+int qrd_gemm_tn_update_even(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
+                            int ldb, double beta, double* C, int ldc, double* slabs, size_t slab_cap, int nwg);
+long long qrd_tn_even_launches(void);       /* even-split launches so far in this process */
+int qrd_tn_even_last_grid(void);            /* workgroups of the last one */
 /* second-generation wide update (qr_gemm_nt.hip): W kept transposed, direct-to-LDS tile loads */
 int qrd_gemm2_init(void);
 int qrd_gemm_nt_ok(int M, int N, int K, const double* A, int lda, const double* Bt, int ldbt, const double* C, int ldc);

@@ -416,11 +416,13 @@ static int plan_create_impl(qr_plan** out, int m, int n, int nb, int ib, int tsq
          * tc0 + tc1*mk/16384 ms at nb = 256); "0" = the panel stream takes no share of the wide update */
         const char* b = lab_getenv("MI355XQR_BALANCE");
         p->bal_rp = 14.0; p->bal_ru = 44.0; p->bal_tc0 = 1.1; p->bal_tc1 = 0.6;
-        if (p->npairs) {            /* measured ~0.22 TFLOP/s per CU for the K = 256 update GEMMs on either side of the partition */
+        if (p->npairs) {            /* measured ~0.22 TFLOP/s per CU for the K = 256 update GEMMs on either side of the partition; the update
+                                     * stream's pair Wt = A2^T (V T), A2 -= V Wt^T at 16384^2 since the even K split of the first: 57.8 and 50.9
+                                     * TFLOP/s in situ on 224 CUs, i.e. 54.1 for the pair = 0.242 per CU (0.23 before; profiles/NOTES.md) */
             int cus = 256;
             qrd_device_info(NULL, 0, &cus, NULL, NULL);
             const int pc = qrd_stream_cus(p->s_pair[0][0]);
-            p->bal_rp = 0.22 * pc; p->bal_ru = 0.23 * (cus - pc);
+            p->bal_rp = 0.22 * pc; p->bal_ru = 0.242 * (cus - pc);
         }
         if (b) {
             p->bal_rp = 0.0;
@@ -1265,7 +1267,7 @@ static int enter_phase(qr_plan* p, int i)
         const int pc = qrd_stream_cus(ns);
         const int uc = nu ? qrd_stream_cus(nu) : cus;
         p->bal_rp = 0.22 * (pc < cus ? pc : 32);
-        p->bal_ru = 0.23 * uc;
+        p->bal_ru = 0.242 * uc;
         const double f = pc <= 32 ? 1.0 : (pc <= 64 ? 0.8 : 0.7);
         p->bal_tc0 = p->bal_tc0_base * f; p->bal_tc1 = p->bal_tc1_base * f;
     }

@@ -22,6 +22,8 @@
 #include "qr_device.h"
 #include "qr_common.h"
 #include "qr_gemm_tile.h"
+#include "qr_tn_even.h"
+#include <atomic>
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int) e_; } while (0)
 
@@ -181,7 +183,10 @@ __global__ __launch_bounds__(512, 4) void gemm_nn_w8_kernel(int M, int N, int K,
 // loop, edge tiles (a workgroup-uniform test) the guarded one.  Before, the ragged strips were launches of their own behind the interior:
 // a row of a few edge tiles, each walking a K slice as long as the interior's, with the chip idle around them (the wide product of a
 // 16448^2 factorisation: 37 TFLOP/s against 55 on the aligned 16384^2).
-template <int TI, int TJ, bool FAST, int TAG = 0, bool MIXED = false>
+// EVEN (with FAST, whole 128 x 128 tiles, K % BK == 0): the even static K split of qr_tn_even.h.  The grid is G workgroups in x; workgroup g
+// walks its own run of (tile, k-tile) units and stores one contiguous 128 x 128 partial (ld 128) per segment at C + slot * 128 * 128, which
+// tile_reduce_kernel sums per tile.  No workgroup waits for or reads what another wrote; one with an empty range writes nothing.
+template <int TI, int TJ, bool FAST, int TAG = 0, bool MIXED = false, bool EVEN = false>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(int M, int N, int K, int kchunk, double alpha,
                                                          const double* __restrict__ A, int lda,
                                                          const double* __restrict__ B, int ldb,
@@ -194,6 +199,30 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(int M, int N, int K, in
     double* Bs = smem + 2 * BM * LDKF;        // [2][BN][LDKF]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wi = wave & 1, wj = wave >> 1;
+    if constexpr (EVEN) {
+        static_assert(FAST && !MIXED && TI == 4 && TJ == 4, "the even split runs whole 128 x 128 tiles on gemm_kloop_il");
+        const int l15 = lane & 15, l4 = lane >> 4;
+        const int gx = M / BM, tiles = gx * (N / BN), nkt = K / BK, G = (int) gridDim.x, U = tiles * nkt;
+        // Workgroups are dealt round-robin to the 8 XCDs; XCD-major ids give each XCD a contiguous run of units, i.e. of tiles that share
+        // their 128 columns of B (tiles are numbered x-fastest), walked at a few distinct k phases: B's k-tiles then hit in that XCD's L2.
+        // Speed only: any bijection of the ids is correct.
+        const int q8 = G >> 3, r8 = G & 7, xcd = (int) blockIdx.x & 7, loc = (int) blockIdx.x >> 3;
+        const int g = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+        const int u1 = tn_even_unit0(g + 1, G, U), rank = tn_even_rank(g, G, U);
+        for (int u = tn_even_unit0(g, G, U); u < u1;) {
+            const tn_even_seg sg = tn_even_seg_at(u, u1, nkt, rank);
+            const int i0 = (sg.tile % gx) * BM, j0 = (sg.tile / gx) * BN;
+            v4d acc[TJ][TI];
+#pragma unroll
+            for (int a = 0; a < TJ; ++a)
+#pragma unroll
+                for (int b = 0; b < TI; ++b) acc[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
+            gemm_kloop_il<TI, TJ>(acc, A, lda, B, ldb, i0, j0, M, N, sg.kt0 * BK, (sg.kt0 + sg.nkt) * BK, As, Bs, tid, wi, wj, l15, l4);
+            gemm_epilogue<TI, TJ, true>(acc, C + (size_t) sg.slot * (BM * BN), BM, BM, BN, 0, 0, 1.0, 0.0, wi, wj, l15, l4);
+            u += sg.nkt;
+        }
+        return;
+    }
     int by = blockIdx.y, bz = blockIdx.z;
     if (gridDim.x == 1 && gridDim.y > 1 && gridDim.y <= 8 && gridDim.z >= 8) {
         // One row of output tiles against a long K split into slices (the tall-skinny update's V^T A2): the column tiles of a K slice all read
@@ -402,6 +431,32 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(int M, int N, int nsla
         }
         double* o = out + (size_t) j * ldo + i0 + tid;
         *o = (beta != 0.0) ? beta * (*o) + v : v;
+    }
+}
+
+// out tile (tx, ty) = sum of that tile's partials of the even split (gemm_tn_kernel<.., EVEN>): slots [first, first + count) of 128 x 128
+// doubles each, ascending in k, added in that order by every thread: deterministic.  blockIdx.x = tile (x-fastest, gx = M / 128 row
+// tiles), blockIdx.y = 16 of its 128 columns; a thread owns four double2.
+__global__ __launch_bounds__(256) void tile_reduce_kernel(int gx, int tiles, int nkt, int G, const double* __restrict__ parts,
+                                                          double* __restrict__ out, int ldo)
+{
+    const int tile = blockIdx.x, tid = threadIdx.x;
+    int first, count;
+    tn_even_tile_slots(tile, G, tiles, nkt, &first, &count);
+    const double* p = parts + (size_t) first * (128 * 128) + (size_t) blockIdx.y * (16 * 128) + 2 * tid;
+    v2d s[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = *reinterpret_cast<const v2d*>(p + 512 * q);
+    for (int z = 1; z < count; ++z) {
+        p += 128 * 128;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] += *reinterpret_cast<const v2d*>(p + 512 * q);
+    }
+    const int i0 = (tile % gx) * 128, j0 = (tile / gx) * 128 + (int) blockIdx.y * 16;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = 2 * tid + 512 * q;                      // element of the 128 x 16 piece, column-major
+        *reinterpret_cast<v2d*>(out + (size_t) (j0 + e / 128) * ldo + i0 + e % 128) = s[q];
     }
 }
 
@@ -817,6 +872,7 @@ int qrd_init(void)
     rc |= allow_lds(gemm_nn_w8_kernel<0>, sizeof(double) * (2 * BK * (128 + 16) + 2 * 128 * LDKF));
     rc |= allow_lds(gemm_nn_w8_kernel<1>, sizeof(double) * (2 * BK * (128 + 16) + 2 * 128 * LDKF));
     rc |= allow_lds(gemm_tn_kernel<4, 4, true, 1>, sizeof(double) * (4 * 128 * LDKF));
+    rc |= allow_lds(gemm_tn_kernel<4, 4, true, 1, false, true>, sizeof(double) * (4 * 128 * LDKF));
     rc |= allow_lds(gemm_tn_kernel<4, 4, true, 3>, sizeof(double) * (4 * 128 * LDKF));
     rc |= allow_lds(gemm_tn_kernel<4, 4, true, 4>, sizeof(double) * (4 * 128 * LDKF));
     rc |= allow_lds(gemm_tn_wide_kernel<1>, sizeof(double) * (2 * (128 + 256) * LDKF));
@@ -909,7 +965,7 @@ int qrd_gemm_nn(void* stream, int M, int N, int K, double alpha, const double* A
 // Tm (optional, M <= 256): C = beta*C + Tm^T * (alpha*A^T*B)   [leaf-level T^T fold].
 static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
                         int ldb, double beta, double* C, int ldc, double* slabs, size_t slab_cap, const double* Tm,
-                        int ldt, int tag);
+                        int ldt, int tag, int even = -1);
 
 // compute units behind a stream (CU-masked streams register themselves; anything else: the whole device)
 // (one table for the process, any device, any host thread: guarded by g_stream_mutex)
@@ -1007,9 +1063,34 @@ int qrd_gemm_tn_update_wide(void* stream, int M, int N, int K, double alpha, con
     return gemm_tn_impl(stream, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, slabs, slab_cap, nullptr, 0, 2);
 }
 
+// the even static K split of the same product (qr_tn_even.h) whenever the shape is eligible, whatever the cost model says, on nwg
+// workgroups (0: two per compute unit of the stream); anything else takes qrd_gemm_tn_update's path (kernel tests, A/B measurements)
+int qrd_gemm_tn_update_even(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
+                            int ldb, double beta, double* C, int ldc, double* slabs, size_t slab_cap, int nwg)
+{
+    return gemm_tn_impl(stream, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, slabs, slab_cap, nullptr, 0, 1, nwg < 0 ? 0 : nwg);
+}
+
+// launches of the even split so far in this process, and the workgroups of the last one (tests: did it run, did the grid follow the stream)
+static std::atomic<long long> g_tn_even_launches{0};
+static std::atomic<int> g_tn_even_last_grid{0};
+long long qrd_tn_even_launches(void) { return g_tn_even_launches.load(); }
+int qrd_tn_even_last_grid(void) { return g_tn_even_last_grid.load(); }
+
+// Modelled cost, in K rows of one workgroup slot like the split-K rule's, of the even split on G workgroups: every workgroup walks
+// ceil(U / G) k-tiles; it pays the fixed cost of a launch's workgroup once and a partial-tile store plus an operand prologue for
+// every further segment (a third of it); the reduce reads G + tiles partial tiles.  G beyond the slots runs in rounds.
+static double tn_even_cost(int tiles, int nkt, int G, int slots, double red_rows_per_tile)
+{
+    const long long U = (long long) tiles * nkt, L = (U + G - 1) / G;
+    const long long nseg = L >= 1 ? (L + nkt - 2) / nkt + 1 : 1;
+    const long long rounds = (G + slots - 1) / slots;
+    return (double) rounds * ((double) L * BK + 96.0 + 32.0 * (double) (nseg - 1)) + (double) (G + tiles) * red_rows_per_tile + 30.0;
+}
+
 static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
                         int ldb, double beta, double* C, int ldc, double* slabs, size_t slab_cap, const double* Tm,
-                        int ldt, int tag)
+                        int ldt, int tag, int even)
 {
     hipStream_t s = (hipStream_t) stream;
     if (M <= 0 || N <= 0) return 0;
@@ -1020,7 +1101,8 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
     // the wide product 32.7 -> 45.7 TFLOP/s; from 4 GFLOP on -- 8200 x 2056 at nb 128, 2 GFLOP per product, loses 3 % to the extra launch)
     if (K % BK != 0 && K >= 16 * BK && Tm == nullptr && vec_ok(A, lda) && vec_ok(B, ldb) && (double) M * N * K >= 4e9) {
         const int Kf = K - K % BK;
-        const int rc0 = gemm_tn_impl(stream, M, N, Kf, alpha, A, lda, B, ldb, beta, C, ldc, slabs, slab_cap, nullptr, 0, tag);
+        // (even = -2: the remainder split keeps the split-K rule for its whole k-tiles, whatever the caller or the model would choose)
+        const int rc0 = gemm_tn_impl(stream, M, N, Kf, alpha, A, lda, B, ldb, beta, C, ldc, slabs, slab_cap, nullptr, 0, tag, -2);
         if (rc0) return rc0;
         return gemm_tn_impl(stream, M, N, K - Kf, alpha, A + Kf, lda, B + Kf, ldb, 1.0, C, ldc, nullptr, 0, nullptr, 0, 0);
     }
@@ -1066,6 +1148,30 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
         const long long wgs = tiles * k, rounds = (wgs + slots - 1) / slots;
         const double cost = (double) rounds * ((double) K / (double) k + 96.0) + (k > 1 ? (double) k * red_rows + 30.0 : 0.0);
         if (cost < best) { best = cost; ksplit = (int) k; }
+    }
+    // The wide update's product (tag 1) on the even static split instead (qr_tn_even.h): G = one round of workgroups, each with the
+    // same number of k-tiles to within one, so there is no round quantisation and one fixed cost per workgroup -- where whole
+    // 128 x 128 tiles, whole k-tiles, alpha 1, beta 0, aligned operands and G + tiles partial tiles in `slabs` allow it, and the model
+    // says it is cheaper than the best ksplit.  MI355XQR_TN_EVEN: 0 never, 1 whenever eligible; `even` >= 0 (qrd_gemm_tn_update_even):
+    // whenever eligible, on that many workgroups; -2 (the K % 16 remainder split above): never.  G = slots; 2 x slots was measured once
+    // against it and lost (profiles/NOTES.md).
+    static const int even_knob = QRD_LAB_ENV_INT("MI355XQR_TN_EVEN", -1);
+    const bool even_forced = even >= 0, even_model = even == -1 && ti == 4 && tj == 4 && !wide && kpipe && even_knob != 0;
+    if (tag == 1 && (even_forced || even_model) && Tm == nullptr && M % 128 == 0 && N % 128 == 0 && K % BK == 0 && K >= BK && alpha == 1.0 &&
+        beta == 0.0 && vec_ok(A, lda) && vec_ok(B, ldb) && vec_ok(C, ldc) && slabs != nullptr && ((uintptr_t) slabs & 15) == 0 &&
+        (long long) (M / 128) * (N / 128) * (K / BK) < (1LL << 31)) {
+        const int etiles = (M / 128) * (N / 128), nkt = K / BK, eslots = 2 * stream_cus(s);
+        const int G = even > 0 ? even : eslots;
+        const bool fits = ((size_t) G + (size_t) etiles) * (128 * 128) <= slab_cap;
+        const double red_tile = 128.0 * 128.0 * 8.0 / 2.0e6 / (2.0 * 128 * 128 / 0.113e6);
+        if (fits && (even_forced || even_knob == 1 || tn_even_cost(etiles, nkt, G, eslots, red_tile) < best)) {
+            hipLaunchKernelGGL((gemm_tn_kernel<4, 4, true, 1, false, true>), dim3(G), dim3(256), sizeof(double) * (4 * 128 * LDKF), s, M, N, K, 0,
+                               1.0, A, lda, B, ldb, 0.0, slabs, 128, (size_t) 0);
+            hipLaunchKernelGGL(tile_reduce_kernel, dim3(etiles, 8), dim3(256), 0, s, M / 128, etiles, nkt, G, slabs, C, ldc);
+            g_tn_even_launches.fetch_add(1);
+            g_tn_even_last_grid.store(G);
+            return (int) hipGetLastError();
+        }
     }
     int kchunk = ((K + ksplit - 1) / ksplit + BK - 1) / BK * BK;
     ksplit = (K + kchunk - 1) / kchunk;

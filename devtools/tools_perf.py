@@ -40,6 +40,8 @@ def run(m, n, nb, ib=32, reps=2):
             p.sync()
             d, a = p.diffnorm(dQR, m, m, n, seed=12)
             line.setdefault("resid", []).append(float((d / a) ** 0.5))
+    if hasattr(q.lib, "qrd_tn_even_launches"):      # wide TN products that took the even static K split, all calls of this process so far
+        line["tn_even_launches"] = int(q.lib.qrd_tn_even_launches())
     print(json.dumps(line), flush=True)
     p.close()
 
