@@ -203,6 +203,15 @@ _sig("qr_gels_damped_wide_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c
      _vp, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _vp, _vp, C.c_int)
 _sig("qr_lsacc_batched_solve_damped_dev", C.c_int, _vp, _vp, _ll, _vp, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _vp, _vp)
 _sig("qr_lstsq_damped_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip)
+_sig("qr_trust_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, C.c_double,
+     C.c_int, C.c_int, _vp, C.c_int, _ll, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
+_sig("qr_gels_trust_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _ll,
+     C.c_double, C.c_int, _vp, C.c_int, _ll, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
+_sig("qr_gels_trust_wide_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _ll, _vp, C.c_int, _ll, _vp, _ll,
+     _vp, _ll, C.c_double, C.c_int, _vp, C.c_int, _ll, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
+_sig("qr_lsacc_batched_solve_trust_dev", C.c_int, _vp, _vp, _ll, _vp, _ll, _vp, _ll, C.c_double, C.c_int, _vp, C.c_int, _ll, _vp, _vp, _vp, _vp,
+     _vp, _vp)
+_sig("qr_lstsq_trust_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -700,6 +709,51 @@ def lstsq_damped_batched(A, B, lam, D=None):
     return X.transpose(0, 1, 3, 2), xnorm, resid, info[:batch].astype(np.int64)
 
 
+def lstsq_trust_batched(A, b, delta, D=None, lam0=None, rtol=0.1, maxit=10):
+    """the trust-region step of every member of A (batch, m, n) and b (batch, m) through qr_lstsq_trust_batched: the lam >= 0 and
+    x = argmin ||A_q x - b_q||^2 + lam^2 ||D_q x||^2 with | ||D x|| - delta | <= rtol delta, or lam = 0 where the Gauss-Newton step is
+    within (1 + rtol) delta (MINPACK lmpar, run on the device).  delta: a scalar or (batch,); D: None (the identity), (n,) or
+    (batch, n), and a wide A (m < n) requires D is None; lam0: None, a scalar or (batch,), the starting guess.  Returns (X, lam, xnorm,
+    resid, iter, status, info): X (batch, n); status 0 converged, 1 Gauss-Newton step accepted, 2 left by the lower-bound clause,
+    3 maxit reached; info 0, i + 1 for a zero on the damped triangle's diagonal, -1 for a delta that is not a finite positive number
+    (that member's other outputs hold nothing).  A member with an info word does not raise."""
+    At = _packed_batch(A, "lstsq_trust_batched")
+    batch, n, m = At.shape
+    b = np.asarray(b, dtype=np.float64)
+    if b.ndim == 3 and b.shape[2] == 1:
+        b = b[:, :, 0]
+    if b.shape != (batch, m):
+        raise QRError(f"lstsq_trust_batched: b must be ({batch}, {m}), one right-hand side per member, got {b.shape}", QR_E_ARG)
+    b = np.ascontiguousarray(b)
+
+    def per_member(v, name):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.broadcast_to(v, (batch,))
+        if v.shape != (batch,):
+            raise QRError(f"lstsq_trust_batched: {name} must be a scalar or ({batch},), got {v.shape}", QR_E_ARG)
+        return np.ascontiguousarray(v)
+
+    delta = per_member(delta, "delta")
+    lam0 = None if lam0 is None else per_member(lam0, "lam0")
+    if D is not None:
+        D = np.asarray(D, dtype=np.float64)
+        if D.ndim == 1:
+            D = np.broadcast_to(D, (batch, D.shape[0]))
+        if D.shape != (batch, n):
+            raise QRError(f"lstsq_trust_batched: D must be ({n},) or ({batch}, {n}), got {D.shape}", QR_E_ARG)
+        D = np.ascontiguousarray(D)
+    X = np.empty((batch, n))
+    lam, xnorm, resid = np.empty(batch), np.empty(batch), np.empty(batch)
+    it, status, info = (np.zeros(max(batch, 1), dtype=np.intc) for _ in range(3))
+    rc = lib.qr_lstsq_trust_batched(_p(At), m, n, _p(b), batch, None if D is None else _p(D), _p(delta), None if lam0 is None else _p(lam0),
+                                    float(rtol), int(maxit), _p(X), _p(lam), _p(xnorm), _p(resid), it.ctypes.data_as(_ip),
+                                    status.ctypes.data_as(_ip), info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_trust_batched")
+    return X, lam, xnorm, resid, it[:batch].astype(np.int64), status[:batch].astype(np.int64), info[:batch].astype(np.int64)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -1040,6 +1094,36 @@ class Plan:
                                                   _dptr(dB), nrhs, ldb, strideB, _dptr(dlam), nlam, stridelam, _dptr(dX), ldx, strideX,
                                                   _dptr(dxnorm), _dptr(dresid), _dptr(dinfo), batch), "qr_gels_damped_wide_batched_dev")
 
+    def trust_batched(self, dR, n, ldr, strideR, dZ, ldz, strideZ, ddelta, stridedelta, dX, ldx, strideX, dlam, dinfo, batch, drss=None,
+                      djpvt=None, stridejpvt=0, dD=None, strideD=0, dlam0=None, stridelam0=0, rtol=0.1, maxit=10, flip=False, dxnorm=None,
+                      dresid=None, diter=None, dstatus=None):
+        """the trust-region step of `batch` members from factors that exist (the operands of damped_batched, one right-hand side): per
+        member the lam >= 0 to dlam and its x to dX with ||D x|| within rtol of ddelta, found inside one launch; dinfo, diter, dstatus:
+        one int per member"""
+        check(lib.qr_trust_batched_dev(self.h, _dptr(dR), n, ldr, strideR, _dptr(dZ), ldz, strideZ, _dptr(drss), _dptr(djpvt), stridejpvt,
+                                       _dptr(dD), strideD, _dptr(ddelta), stridedelta, _dptr(dlam0), stridelam0, float(rtol), int(maxit),
+                                       int(bool(flip)), _dptr(dX), ldx, strideX, _dptr(dlam), _dptr(dxnorm), _dptr(dresid), _dptr(diter),
+                                       _dptr(dstatus), _dptr(dinfo), batch), "qr_trust_batched_dev")
+
+    def gels_trust_batched(self, dA, m, n, lda, strideA, dtau, stridetau, dB, ldb, strideB, ddelta, stridedelta, dX, ldx, strideX, dlam, dinfo,
+                           batch, dD=None, strideD=0, dlam0=None, stridelam0=0, rtol=0.1, maxit=10, dxnorm=None, dresid=None, diter=None,
+                           dstatus=None):
+        """m >= n: dA factored in place (as geqrf_batched leaves it), dB (m rows) <- Q^T b in all rows, then the trust-region step"""
+        check(lib.qr_gels_trust_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, _dptr(dB), ldb, strideB, _dptr(dD),
+                                            strideD, _dptr(ddelta), stridedelta, _dptr(dlam0), stridelam0, float(rtol), int(maxit), _dptr(dX),
+                                            ldx, strideX, _dptr(dlam), _dptr(dxnorm), _dptr(dresid), _dptr(diter), _dptr(dstatus),
+                                            _dptr(dinfo), batch), "qr_gels_trust_batched_dev")
+
+    def gels_trust_wide_batched(self, dA, m, n, lda, strideA, dF, ldf, strideF, dtau, stridetau, dB, ldb, strideB, ddelta, stridedelta, dX, ldx,
+                                strideX, dlam, dinfo, batch, dlam0=None, stridelam0=0, rtol=0.1, maxit=10, dxnorm=None, dresid=None,
+                                diter=None, dstatus=None):
+        """m < n, D = I: dA untouched, the factors of A^T to dF and dtau, dB (m rows) read only, the minimum-norm step of length within
+        rtol of ddelta (n rows) to dX"""
+        check(lib.qr_gels_trust_wide_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dF), ldf, strideF, _dptr(dtau), stridetau,
+                                                 _dptr(dB), ldb, strideB, _dptr(ddelta), stridedelta, _dptr(dlam0), stridelam0, float(rtol),
+                                                 int(maxit), _dptr(dX), ldx, strideX, _dptr(dlam), _dptr(dxnorm), _dptr(dresid), _dptr(diter),
+                                                 _dptr(dstatus), _dptr(dinfo), batch), "qr_gels_trust_wide_batched_dev")
+
     def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
         """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""
         check(lib.qr_geqrf_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, batch), "qr_geqrf_batched_dev")
@@ -1307,6 +1391,13 @@ class LsAccumulatorBatched:
         """the damped solves of every member from the state, which stays untouched: dX n x (nlam * nrhs) per member, dinfo nlam ints"""
         check(lib.qr_lsacc_batched_solve_damped_dev(self.h, _dptr(dD), strideD, _dptr(dlam), nlam, stridelam, _dptr(dX), ldx, strideX,
                                                     _dptr(dxnorm), _dptr(dresid), _dptr(dinfo)), "qr_lsacc_batched_solve_damped_dev")
+
+    def solve_trust(self, ddelta, stridedelta, dX, ldx, strideX, dlam, dinfo, dD=None, strideD=0, dlam0=None, stridelam0=0, rtol=0.1, maxit=10,
+                    dxnorm=None, dresid=None, diter=None, dstatus=None):
+        """the trust-region step of every member from the state (nrhs == 1), which stays untouched"""
+        check(lib.qr_lsacc_batched_solve_trust_dev(self.h, _dptr(dD), strideD, _dptr(ddelta), stridedelta, _dptr(dlam0), stridelam0, float(rtol),
+                                                   int(maxit), _dptr(dX), ldx, strideX, _dptr(dlam), _dptr(dxnorm), _dptr(dresid), _dptr(diter),
+                                                   _dptr(dstatus), _dptr(dinfo)), "qr_lsacc_batched_solve_trust_dev")
 
     def reset(self):
         check(lib.qr_lsacc_batched_reset(self.h), "qr_lsacc_batched_reset")

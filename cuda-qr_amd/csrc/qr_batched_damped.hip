@@ -24,26 +24,6 @@
 
 static_assert(QRD_B_MAX_N == 64, "one lane per row of the triangle");
 
-// what a lane needs beside its rows: d of its column (through jpvt), the row of X its x goes to, and rss of right-hand side `lane`
-struct bd_lane {
-    double dsc, rss;
-    int perm;
-};
-
-// lane < n: jp = jpvt[lane] (clamped into the block: a jpvt that is none of geqp3's must not carry a store out of it)
-__device__ __forceinline__ void bd_lane_setup(const qrd_bd_args& a, size_t q, int lane, bd_lane& L)
-{
-    const int n = a.n;
-    int jp = lane < n ? lane : 0;
-    if (a.jpvt && lane < n) {
-        const int v = a.jpvt[q * a.sj + lane];
-        if (v >= 0 && v < n) jp = v;
-    }
-    L.dsc = (a.D && lane < n) ? a.D[q * a.sD + jp] : 1.0;
-    L.perm = a.flip ? n - 1 - lane : jp;
-    L.rss = (a.rss && lane < a.nrhs) ? a.rss[q * (size_t) a.nrhs + lane] : 0.0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // wave route: the lambda loop.  r[]: lane i < n holds row i of the master [R | Z], zeros below the diagonal and in lanes >= n.  Rs, Xs:
 // this wave's LDS, W x (W + 1) doubles each.
@@ -58,34 +38,8 @@ __device__ __forceinline__ void bd_wave_lams(const double (&r)[W], const qrd_bd_
     double* Xq = a.X + q * a.sX;
     for (int k = 0; k < nlam; ++k) {
         const double sd = lamq[k] * L.dsc;    // lane j: S(j, j)
-        double w[W], s[W];
-#pragma unroll
-        for (int c = 0; c < W; ++c) {
-            w[c] = r[c];
-            s[c] = (c < n && lane == c) ? sd : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-            if (j < n) {                      // (wave-uniform)
-                const double x = s[j];        // (rows > j of the block's column j are exact zeros)
-                const double ssq = qb_wave_sum(x * x);
-                if (ssq != 0.0) {             // (the same value in every lane)
-                    const double alpha = qb_bcast(w[j], j);
-                    double beta, scal;
-                    const double tj = qb_larfg(alpha, ssq, beta, scal);
-                    const double v = x * scal;
-#pragma unroll
-                    for (int c = j + 1; c < W; ++c) {
-                        if (c < ntot) {
-                            const double tw = tj * (qb_bcast(w[c], j) + qb_wave_sum(v * s[c]));
-                            if (lane == j) w[c] -= tw;
-                            s[c] = fma(-tw, v, s[c]);
-                        }
-                    }
-                    if (lane == j) w[j] = beta;
-                }
-            }
-        }
+        double w[W];
+        bd_wave_elim<W>(r, sd, n, ntot, lane, w);
         double diag = 1.0;
 #pragma unroll
         for (int c = 0; c < W; ++c)
@@ -113,7 +67,7 @@ __device__ __forceinline__ void bd_wave_lams(const double (&r)[W], const qrd_bd_
                 for (int i = n + lane; i < a.xrows; i += 64) xc[i] = 0.0;
                 if (a.xnorm) {
                     const double dx = L.dsc * xi;
-                    const double s2 = qb_wave_sum(dx * dx);
+                    const double s2 = bd_wave_dot(dx, dx);
                     if (lane == 0) a.xnorm[q * (size_t) nlam * nrhs + col] = sqrt(s2);
                 }
                 if (a.resid) {
@@ -125,7 +79,7 @@ __device__ __forceinline__ void bd_wave_lams(const double (&r)[W], const qrd_bd_
                     for (int cc = 0; cc < W; ++cc)
                         if (cc < n) t = fma(r[cc], Xs[kk * LW + cc], t);
                     t = lane < n ? t : 0.0;
-                    const double s2 = qb_wave_sum(t * t);
+                    const double s2 = bd_wave_dot(t, t);
                     const double rs = qb_bcast(L.rss, kk);
                     if (lane == 0) a.resid[q * (size_t) nlam * nrhs + col] = sqrt(s2 + rs);
                 }
@@ -142,32 +96,10 @@ __global__ void __launch_bounds__(256) bd_wave_kernel(const qrd_bd_args a)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t q = (size_t) blockIdx.x * 4 + wv;
     if (q >= (size_t) a.batch) return;        // (no workgroup barrier below: the waves of a workgroup are independent)
-    const int n = a.n, nrhs = a.nrhs, ntot = n + nrhs;
-    const double* Rq = a.R + q * a.sR;
-    const double* Zq = a.Z + q * a.sZ;
     bd_lane L;
     bd_lane_setup(a, q, lane, L);
-    const int src = a.flip ? n - 1 - lane : lane;     // flip: U(i, c) = R(n-1-c, n-1-i), z reversed
     double r[W];
-#pragma unroll
-    for (int c = 0; c < W; ++c) {
-        double v = 0.0;
-        if (lane < n && c < n) {
-            if (lane <= c) v = a.flip ? Rq[(size_t) src * a.ldr + (n - 1 - c)] : Rq[(size_t) c * a.ldr + lane];      // (the strict lower triangle is not read)
-        } else if (lane < n && c < ntot) {
-            v = Zq[(size_t) (c - n) * a.ldz + src];
-        }
-        r[c] = v;
-    }
-    if (a.zrows > n) {                        // the tail of Q^T b: rows n .. zrows-1 of every right-hand side
-        for (int kk = 0; kk < nrhs; ++kk) {
-            const double* zc = Zq + (size_t) kk * a.ldz;
-            double t = 0.0;
-            for (int i = n + lane; i < a.zrows; i += 64) t = fma(zc[i], zc[i], t);
-            t = qb_wave_sum(t);
-            if (lane == kk) L.rss += t;
-        }
-    }
+    bd_wave_load<W>(a, q, lane, r, L);
     constexpr int LW = W + 1;
     double* Rs = sm + (size_t) wv * 2 * W * LW;
     bd_wave_lams<W>(r, a, q, lane, L, Rs, Rs + W * LW);
@@ -182,53 +114,17 @@ __global__ void __launch_bounds__(256) bd_fused_wave_kernel(double* __restrict__
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t q = (size_t) blockIdx.x * 4 + wv;
     if (q >= (size_t) a.batch) return;        // (no workgroup barrier below)
-    const int n = a.n, nrhs = a.nrhs, ntot = n + nrhs;
-    double* Aq = A + q * strideA;
-    double* Bq = B + q * a.sZ;
-    const bool row = lane < m;
-    double r[W];
-#pragma unroll
-    for (int c = 0; c < W; ++c) {
-        double v = 0.0;
-        if (row && c < n) v = Aq[(size_t) c * lda + lane];
-        else if (row && c < ntot) v = Bq[(size_t) (c - n) * a.ldz + lane];
-        r[c] = v;
-    }
-    double tauv = 0.0, diag = 1.0;
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-        if (j < n) qb_wave_col<W>(r, j, ntot, lane, tauv, diag);      // (wave-uniform; B's columns ride along)
-    }
     bd_lane L;
-    bd_lane_setup(a, q, lane, L);
-    L.rss = 0.0;
-#pragma unroll
-    for (int c = 0; c < W; ++c) {
-        if (c < n) {
-            if (row) Aq[(size_t) c * lda + lane] = r[c];
-            r[c] = (lane < n && lane <= c) ? r[c] : 0.0;         // the master: R alone, V and the rows below it gone
-        } else if (c < ntot) {
-            if (row) Bq[(size_t) (c - n) * a.ldz + lane] = r[c];
-            const double y = lane >= n ? r[c] : 0.0;             // (rows >= m hold zeros)
-            const double t = qb_wave_sum(y * y);
-            if (lane == c - n) L.rss = t;
-            r[c] = lane < n ? r[c] : 0.0;
-        }
-    }
-    if (lane < n) tau[q * stridetau + lane] = tauv;
+    double r[W];
+    bd_wave_factor<W>(A + q * strideA, m, lda, tau + q * stridetau, B + q * a.sZ, a, q, lane, r, L);
     constexpr int LW = W + 1;
     double* Rs = sm + (size_t) wv * 2 * W * LW;
     bd_wave_lams<W>(r, a, q, lane, L, Rs, Rs + W * LW);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// workgroup route.  LDS: Ms, Ws, Ss (n x (n + nrhs) each at ld = bd_ld(n): the master [R | Z], the working copy, the block), then
-// dsc[64], rss[64], perm[64] (ints), a word for info.
+// workgroup route: the images and words of bd_wg_lds (qr_batched_dev.h)
 // ---------------------------------------------------------------------------------------------------------------------------------
-__host__ __device__ constexpr int bd_ld(int n) { return n | 1; }
-__host__ __device__ constexpr size_t bd_wg_lds(int n, int ntot) { return sizeof(double) * (3 * (size_t) ntot * bd_ld(n) + 2 * 64 + 32 + 2); }
-static_assert(bd_wg_lds(63, 64) <= QB_LDS_CAP && bd_wg_lds(32, 64) <= QB_LDS_CAP, "the three images fit");
-
 __global__ void __launch_bounds__(256) bd_wg_kernel(const qrd_bd_args a)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -242,65 +138,12 @@ __global__ void __launch_bounds__(256) bd_wg_kernel(const qrd_bd_args a)
     double* rssv = dsc + 64;
     int* perm = (int*) (rssv + 64);
     int* sinfo = perm + 64;
-    const double* Rq = a.R + q * a.sR;
-    const double* Zq = a.Z + q * a.sZ;
     const double* lamq = a.lam + q * a.slam;
     double* Xq = a.X + q * a.sX;
-    for (int idx = t; idx < ntot * n; idx += 256) {
-        const int c = idx / n, i = idx - c * n;
-        const int src = a.flip ? n - 1 - i : i;
-        double v = 0.0;
-        if (c >= n) v = Zq[(size_t) (c - n) * a.ldz + src];
-        else if (i <= c) v = a.flip ? Rq[(size_t) src * a.ldr + (n - 1 - c)] : Rq[(size_t) c * a.ldr + i];
-        Ms[c * ld + i] = v;
-    }
-    if (wv == 0) {                            // (n, nrhs < 64: one lane each)
-        bd_lane L;
-        bd_lane_setup(a, q, lane, L);
-        dsc[lane] = L.dsc;
-        perm[lane] = L.perm;
-        rssv[lane] = L.rss;
-    }
-    __syncthreads();
-    if (a.zrows > n) {
-        for (int kk = wv; kk < nrhs; kk += 4) {
-            const double* zc = Zq + (size_t) kk * a.ldz;
-            double s = 0.0;
-            for (int i = n + lane; i < a.zrows; i += 64) s = fma(zc[i], zc[i], s);
-            s = qb_wave_sum(s);
-            if (lane == 0) rssv[kk] += s;
-        }
-    }
+    bd_wg_load(a, q, t, Ms, ld, dsc, rssv, perm);
     for (int k = 0; k < nlam; ++k) {
         const double lam = lamq[k];
-        __syncthreads();                      // (the images of the previous lambda are read no more; dsc and rssv are written)
-        for (int idx = t; idx < ntot * n; idx += 256) {
-            const int c = idx / n, i = idx - c * n;
-            Ws[c * ld + i] = Ms[c * ld + i];
-            Ss[c * ld + i] = (c == i) ? lam * dsc[i] : 0.0;
-        }
-        __syncthreads();
-        for (int j = 0; j < n; ++j) {
-            // every wave forms the norm and the scalars from the same LDS words: the same values in all 256 threads
-            const double x = lane <= j ? Ss[j * ld + lane] : 0.0;
-            const double ssq = qb_wave_sum(x * x);
-            double beta = 0.0;
-            if (ssq != 0.0) {
-                const double alpha = Ws[j * ld + j];
-                double scal;
-                const double tj = qb_larfg(alpha, ssq, beta, scal);
-                const double v = x * scal;
-                for (int c = j + 1 + wv; c < ntot; c += 4) {     // wave wv: columns j + 1 + wv, + 4, ..
-                    double* sc = Ss + c * ld;
-                    const double sv = lane <= j ? sc[lane] : 0.0;
-                    const double tw = tj * (Ws[c * ld + j] + qb_wave_sum(v * sv));
-                    if (lane <= j) sc[lane] = fma(-tw, v, sv);
-                    if (lane == 0) Ws[c * ld + j] -= tw;         // (read by every lane above: the wave runs in lock step up to the butterfly)
-                }
-            }
-            __syncthreads();                  // (alpha and column j of the block are read no more)
-            if (t == 0 && ssq != 0.0) Ws[j * ld + j] = beta;    // (read next by thread 0 below, by the others after a barrier)
-        }
+        bd_wg_elim(Ms, Ws, Ss, dsc, lam, n, ntot, ld, t);
         if (t == 0) a.info[q * (size_t) nlam + k] = *sinfo = qb_info_serial(Ws, ld, n);
         __syncthreads();
         if (*sinfo) continue;                 // (the same word in every thread: nothing else is written for this pair)
@@ -315,7 +158,7 @@ __global__ void __launch_bounds__(256) bd_wg_kernel(const qrd_bd_args a)
             for (int i = n + lane; i < a.xrows; i += 64) xc[i] = 0.0;
             if (a.xnorm) {
                 const double dx = lane < n ? dsc[lane] * xi : 0.0;
-                const double s2 = qb_wave_sum(dx * dx);
+                const double s2 = bd_wave_dot(dx, dx);
                 if (lane == 0) a.xnorm[q * (size_t) nlam * nrhs + col] = sqrt(s2);
             }
             if (a.resid) {
@@ -324,7 +167,7 @@ __global__ void __launch_bounds__(256) bd_wg_kernel(const qrd_bd_args a)
                     e = -Ms[(n + kk) * ld + lane];
                     for (int cc = lane; cc < n; ++cc) e = fma(Ms[cc * ld + lane], xs[cc], e);
                 }
-                const double s2 = qb_wave_sum(e * e);
+                const double s2 = bd_wave_dot(e, e);
                 if (lane == 0) a.resid[q * (size_t) nlam * nrhs + col] = sqrt(s2 + rssv[kk]);
             }
         }

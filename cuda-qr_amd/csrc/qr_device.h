@@ -382,6 +382,28 @@ int qrd_bd_wave_route(int ncols);
 int qrd_bd_solve(void* stream, const qrd_bd_args* a);
 int qrd_bd_fused(void* stream, double* A, int m, int lda, size_t strideA, double* tau, size_t stridetau, double* B, const qrd_bd_args* a);
 
+/* batched trust-region step (qr_batched_trust.hip, called from qr_batched_trust.c only; mi355x_qr.h section 8g).  Per member the lambda
+ * >= 0 with | |D x| - delta | <= rtol delta (or lambda = 0 and |D x| <= (1 + rtol) delta) by MINPACK lmpar's iteration on lambda^2,
+ * every elimination being the one qrd_bd_solve runs.
+ *   d: the operands of qrd_bd_args with nrhs = 1 and nlam = 1; d.lam is not referenced; X has one column, xnorm, resid and info one
+ *   entry per member.  delta (one per member, sdelta apart, 0: shared), lam0 (the starting guess, slam0 apart, 0: shared; NULL: 0), rtol in
+ *   (0, 1), maxit >= 1.  lam (the lambda found), iter (the eliminations run; may be NULL), status (0 converged, 1 the Gauss-Newton step
+ *   accepted, 2 left by the lower-bound clause, 3 maxit reached; may be NULL): one per member, packed.  info: 0; i + 1 for the smallest i
+ *   with R~(i,i) == 0 in an elimination; -1 for a delta that is not a finite positive number; nothing else is written then.
+ * qrd_bt_solve: one launch, a wave per member for n + 1 <= 32, else a workgroup per member (n <= 63).  qrd_bt_fused: m <= 64 and
+ * n + 1 <= 32 only, the factorisation of qrd_bd_fused in front of the same search.  batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_bt_args {
+    qrd_bd_args d;
+    const double *delta, *lam0;
+    double* lam;
+    int *iter, *status;
+    size_t sdelta, slam0;
+    double rtol;
+    int maxit;
+} qrd_bt_args;
+int qrd_bt_solve(void* stream, const qrd_bt_args* a);
+int qrd_bt_fused(void* stream, double* A, int m, int lda, size_t strideA, double* tau, size_t stridetau, double* B, const qrd_bt_args* a);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

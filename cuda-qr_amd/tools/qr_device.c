@@ -911,9 +911,81 @@ static int batched_damped_main(int m, int n, int count, int nlam)
     return 0;
 }
 
+/* count matrices of m x n through one trust-region call with Delta = frac x the Gauss-Newton |x| of each member */
+static int batched_trust_main(int m, int n, int count, double frac)
+{
+    if (n < 1 || n >= QR_BATCHED_MAX_N || m < n || count < 1 || !(frac > 0.0)) {
+        fprintf(stderr, "--batched count --trust frac needs count >= 1, frac > 0 and 1 <= n < %d, n <= m\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d matrices of %dx%d, Delta = %g x the Gauss-Newton step\n", count, m, n, frac);
+    const size_t mn = (size_t) m * n, cnt = mn * count, nc = (size_t) count;
+    double *A = malloc(sizeof(double) * cnt), *B = malloc(sizeof(double) * (size_t) m * count);
+    double *delta = malloc(sizeof(double) * nc), *xn = malloc(sizeof(double) * nc);
+    int *info = malloc(sizeof(int) * nc), *iter = malloc(sizeof(int) * nc);
+    if (!A || !B || !delta || !xn || !info || !iter) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < cnt; i++) A[i] = (double) rand() / RAND_MAX - 0.5;
+    for (size_t i = 0; i < (size_t) m * count; i++) B[i] = (double) rand() / RAND_MAX - 0.5;
+    const double zero = 0.0;
+    qr_plan* p = NULL;
+    double *dA = NULL, *dB = NULL, *dtau = NULL, *dX = NULL, *dv = NULL;
+    int* di = NULL;
+    if (qr_plan_create(&p, m, n, 0, 0) || qr_device_malloc((void**) &dA, sizeof(double) * cnt) ||
+        qr_device_malloc((void**) &dB, sizeof(double) * (size_t) m * count) || qr_device_malloc((void**) &dtau, sizeof(double) * (size_t) n * count) ||
+        qr_device_malloc((void**) &dX, sizeof(double) * (size_t) n * count) || qr_device_malloc((void**) &dv, sizeof(double) * (3 * nc + 1)) ||
+        qr_device_malloc((void**) &di, sizeof(int) * 2 * nc) || qr_copy_to_device(dv + 3 * nc, &zero, sizeof(double))) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    double *ddelta = dv, *dlam = dv + nc, *dxn = dv + 2 * nc;
+    double el = 0.0;
+    for (int t = -2; t < TRIALS; t++) {               /* t == -2: the Gauss-Newton |x| of every member (lambda = 0), which sets the radii */
+        if (qr_copy_to_device(dA, A, sizeof(double) * cnt) || qr_copy_to_device(dB, B, sizeof(double) * (size_t) m * count)) {
+            fprintf(stderr, "copy failed\n");
+            return 1;
+        }
+        const double t0 = now();
+        int rc = t == -2 ? qr_gels_damped_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dB, 1, m, m, NULL, 0, dv + 3 * nc, 1, 0, dX, n, n, dxn,
+                                                      NULL, di, count)
+                         : qr_gels_trust_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dB, m, m, NULL, 0, ddelta, 1, NULL, 0, 0.1, 10, dX, n,
+                                                     n, dlam, dxn, NULL, di + nc, NULL, di, count);
+        if (!rc) rc = qr_plan_sync(p);
+        if (rc) {
+            fprintf(stderr, "the batched call failed: %s%s\n", qr_strerror(rc), rc == QR_E_ARG ? " (the shape does not fit: see qr_batched_max_rows)" : "");
+            return 1;
+        }
+        if (t >= 0) el += now() - t0;
+        if (t == -2) {
+            if (qr_copy_to_host(xn, dxn, sizeof(double) * nc)) { fprintf(stderr, "copy back failed\n"); return 1; }
+            for (size_t q = 0; q < nc; q++) delta[q] = frac * xn[q];
+            if (qr_copy_to_device(ddelta, delta, sizeof(double) * nc)) { fprintf(stderr, "copy failed\n"); return 1; }
+        }
+    }
+    if (qr_copy_to_host(xn, dxn, sizeof(double) * nc) || qr_copy_to_host(info, di, sizeof(int) * nc) || qr_copy_to_host(iter, di + nc, sizeof(int) * nc)) {
+        fprintf(stderr, "copy back failed\n");
+        return 1;
+    }
+    int failed = 0, most = 0;
+    double worst = 0.0;
+    for (size_t q = 0; q < nc; q++) {
+        if (info[q]) { failed++; continue; }
+        if (iter[q] > most) most = iter[q];
+        const double e = fabs(xn[q] - delta[q]) / delta[q];
+        if (iter[q] > 0 && e > worst) worst = e;    /* (a member whose Gauss-Newton step lies inside the radius keeps it) */
+    }
+    printf(" MMQR ran trust-region steps of %d %dx%d systems in %f s (avg over %d)   [batch resident in HBM, rtol 0.1, maxit 10]\n", count, m, n,
+           el / TRIALS, TRIALS);
+    printf(" failed = %d   worst | |x| - Delta | / Delta = %.2e   most iterations = %d\n", failed, worst, most);
+    qr_device_free(dA); qr_device_free(dB); qr_device_free(dtau); qr_device_free(dX); qr_device_free(dv); qr_device_free(di);
+    qr_plan_destroy(p);
+    free(A); free(B); free(delta); free(xn); free(info); free(iter);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -939,6 +1011,9 @@ int main(int argc, char** argv)
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--damped") == 0)
                     return batched_damped_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atoi(argv[k + 1]) : 1);
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--trust") == 0)
+                    return batched_trust_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atof(argv[k + 1]) : 0.5);
             return batched_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
         }
     for (int i = 3; i < argc; i++)

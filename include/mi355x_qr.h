@@ -981,9 +981,8 @@ int qr_lstsq_minnorm_batched(const double* A, int m, int n, const double* B, int
  * Routes.  n + nrhs <= 32: one wave per member, four members per workgroup, lane i holding row i of the factors, of the working copy
  * and of the block in registers.  Otherwise (n + nrhs <= QR_BATCHED_MAX_N): one workgroup per member with the three images in LDS.
  *
- * Out of scope: a trust-region search for lambda on the device (MINPACK lmpar, which finds |D x| ~ Delta by Newton steps; dxnorm is
- * the value it needs); a general D for wide members; a fused launch on the workgroup route; generalised cross-validation; blocked /
- * MFMA variants.
+ * Out of scope: a general D for wide members; a fused launch on the workgroup route; generalised cross-validation; blocked / MFMA
+ * variants.  (The trust-region search for lambda is section 8g.)
  * ------------------------------------------------------------------------------------------- */
 
 /* The damped solves from factors that exist, one launch.  dR: n x n, ldr >= n, only the upper triangle is read; dZ: n x nrhs, ldz >= n,
@@ -1035,6 +1034,98 @@ int qr_lsacc_batched_solve_damped_dev(qr_lsacc_batched* acc, const double* dD, l
 int qr_lstsq_damped_batched(const double* A, int m, int n, const double* B, int nrhs, int batch,
                             const double* D, const double* lam, int nlam,
                             double* X, double* xnorm, double* resid, int* info);
+
+/* ---------------------------------------------------------------------------------------------
+ * 8g. Batched trust-region step: the lambda of section 8f found on the device.  Per member, given a radius Delta > 0, the calls find
+ * lambda >= 0 and x = argmin |A x - b|^2 + lambda^2 |D x|^2 such that either lambda = 0 and |D x| <= (1 + rtol) Delta, or
+ * | |D x| - Delta | <= rtol Delta -- the inner step of a batched Levenberg-Marquardt solver (per-pixel curve fitting, damped inverse
+ * kinematics with a step limit), whose callers hold a radius per member, not a lambda.  One right-hand side per member: several would
+ * each need a lambda of their own.  The whole search of every member runs inside one launch; members take different numbers of
+ * iterations side by side and nothing waits on the host.
+ *
+ * The method is MINPACK lmpar (More 1978) with MINPACK's par = lambda^2; it iterates on par, and reports and eliminates with
+ * lambda = sqrt(par).
+ *   1. Gauss-Newton step.  nsing = the first i with R(i,i) == 0 exactly, or n.  x solves the leading nsing x nsing system, the rest of x
+ *      is 0.  fp = |D x| - Delta.  fp <= rtol Delta: lambda = 0, iter = 0, status 1, done.
+ *   2. Bounds.  parl = fp / (Delta |w|^2) with R^T w = D^2 x / |D x| (in pivoted order) if nsing == n, else 0.  paru = |g| / Delta with
+ *      g_j = (sum over i <= j of R(i,j) z_i) / d[jpvt[j]] (a column with d == 0 contributes nothing); if that is 0, paru = DBL_MIN /
+ *      min(Delta, 0.1).
+ *   3. Start.  par = min(max(lambda0^2, parl), paru); if par == 0, par = |g| / |D x|.
+ *   4. At most maxit iterations: if par == 0, par = max(DBL_MIN, 0.001 paru); lambda = sqrt(par); section 8f's elimination of
+ *      lambda D against the untouched factors, the same arithmetic in the same order; R~ x = z~; fp = |D x| - Delta.  Leave with status 0
+ *      if |fp| <= rtol Delta; with status 2 if parl == 0 and fp <= the previous fp < 0; with status 3 if the count is reached.  Otherwise
+ *      R~^T w = D^2 x / |D x|, parc = fp / (Delta |w|^2); fp > 0 raises parl to par, fp < 0 lowers paru to par; par = max(parl, par + parc).
+ * MINPACK's constants are rtol = 0.1 and maxit = 10; here 0 < rtol < 1 and maxit >= 1 are arguments.
+ *
+ * Section 8's conventions hold as in 8f, and jpvt, dD, flip, drss and the stride rules are exactly qr_damped_batched_dev's.  ddelta and
+ * dlam0 (the starting guess for lambda; may be NULL: 0) hold one double per member; a stride of 0 means shared, any other must be >= 1.
+ *
+ * Per member the calls write: dX (n rows, one column, ldx >= n, strideX >= ldx), dlam (the lambda found), dxnorm = |D x|, dresid (as in
+ * 8f: sqrt(|R x - z|^2 + rss) from the untouched factors), diter (the number of eliminations), dstatus (0 converged; 1 the Gauss-Newton
+ * step accepted, lambda = 0; 2 left by the lower-bound clause, MINPACK's exit on a singular R; 3 maxit reached) and dinfo: 0; i + 1 for
+ * an exactly zero R~(i,i) in an elimination, as in 8f; -1 for a member whose Delta is not a finite positive number.  One entry per
+ * member each, packed; dxnorm, dresid, diter and dstatus may be NULL.  A member with info != 0 has nothing else written; its neighbours
+ * are unaffected and the call returns 0.  Because the elimination runs on the stored, rounded lambda = sqrt(par), the X, xnorm and resid
+ * of a member are bitwise what qr_damped_batched_dev returns for the lambda in dlam.
+ *
+ * Routes.  n + 1 <= 32: one wave per member, four members per workgroup, the layout of 8f's wave route; every loop decision is taken on
+ * a value that a wave butterfly left identical in all lanes.  Otherwise (n <= QR_BATCHED_MAX_N - 1): one workgroup per member with 8f's
+ * three LDS images, thread 0 publishing every decision in an LDS word that all threads read after a barrier.  Both compile to no
+ * scratch memory.
+ *
+ * Out of scope: the outer Levenberg-Marquardt loop (the Jacobian, the gain ratio, the update of Delta); several right-hand sides per
+ * member; a general D for wide members; a fused launch on the workgroup route; blocked / MFMA variants of the elimination.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The step from factors that exist, one launch.  dR: n x n, ldr >= n, only the upper triangle is read; dZ: n rows, ldz >= n, strideZ >=
+ * ldz, the top of Q^T b; drss (may be NULL: 0): one double per member.  1 <= n <= QR_BATCHED_MAX_N - 1. */
+int qr_trust_batched_dev(qr_plan* plan, const double* dR, int n, int ldr, long long strideR,
+                         const double* dZ, int ldz, long long strideZ, const double* drss,
+                         const int* djpvt, long long stridejpvt, const double* dD, long long strideD,
+                         const double* ddelta, long long stridedelta, const double* dlam0, long long stridelam0,
+                         double rtol, int maxit, int flip,
+                         double* dX, int ldx, long long strideX, double* dlam, double* dxnorm, double* dresid,
+                         int* diter, int* dstatus, int* dinfo, int batch);
+
+/* m >= n: factor and search.  dA, dtau and dB (m rows, ldb >= m; Q^T b in all rows on return) come back as
+ * qr_gels_damped_batched_dev leaves them; the shape limits are its own with nrhs = 1.  ONE launch for m <= 64 and n + 1 <= 32 (section
+ * 8's wave factorisation of [A | b], then the same search on the registers the factors are in; where the Gauss-Newton step is accepted
+ * X is bitwise qr_gels_batched_dev's); otherwise qr_geqrf_batched_dev, qr_ormqr_batched_dev 'T' and qr_trust_batched_dev: three. */
+int qr_gels_trust_batched_dev(qr_plan* plan, double* dA, int m, int n, int lda, long long strideA,
+                              double* dtau, long long stridetau, double* dB, int ldb, long long strideB,
+                              const double* dD, long long strideD,
+                              const double* ddelta, long long stridedelta, const double* dlam0, long long stridelam0,
+                              double rtol, int maxit,
+                              double* dX, int ldx, long long strideX, double* dlam, double* dxnorm, double* dresid,
+                              int* diter, int* dstatus, int* dinfo, int batch);
+
+/* m < n with D = I: a minimum-norm step of bounded length (inverse kinematics with a step limit).  x = Q [y ; 0] with A^T = Q R and
+ * |x| = |y|, so the radius applies to y.  The operands and limits are qr_gels_damped_wide_batched_dev's with nrhs = 1 (m <=
+ * QR_BATCHED_MAX_N - 1); dX has n rows, ldx >= n.  Four launches: transpose, geqrf, the search with flip writing [y ; 0], one ormqr 'N'
+ * -- which also runs over the column of a member with an info word: that holds no solution. */
+int qr_gels_trust_wide_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda, long long strideA,
+                                   double* dF, int ldf, long long strideF, double* dtau, long long stridetau,
+                                   const double* dB, int ldb, long long strideB,
+                                   const double* ddelta, long long stridedelta, const double* dlam0, long long stridelam0,
+                                   double rtol, int maxit,
+                                   double* dX, int ldx, long long strideX, double* dlam, double* dxnorm, double* dresid,
+                                   int* diter, int* dstatus, int* dinfo, int batch);
+
+/* qr_trust_batched_dev on the state of a batched accumulator (section 8d) with nrhs == 1: its R, Z and sums, one launch, the state
+ * untouched. */
+int qr_lsacc_batched_solve_trust_dev(qr_lsacc_batched* acc, const double* dD, long long strideD,
+                                     const double* ddelta, long long stridedelta, const double* dlam0, long long stridelam0,
+                                     double rtol, int maxit,
+                                     double* dX, int ldx, long long strideX, double* dlam, double* dxnorm, double* dresid,
+                                     int* diter, int* dstatus, int* dinfo);
+
+/* The step of a packed batch on host pointers (A: m x n, b: m per member, both untouched; D: n per member or NULL; delta: one per member;
+ * lam0: one per member or NULL): X n per member, lam, and xnorm, resid, iter, status (any may be NULL), info, one per member.  m >= n
+ * goes the tall route, m < n the wide route, which requires D == NULL.  iter and status of a member with an info word read 0.  Returns
+ * QR_E_SINGULAR if any info entry is non-zero.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_trust_batched(const double* A, int m, int n, const double* b, int batch,
+                           const double* D, const double* delta, const double* lam0, double rtol, int maxit,
+                           double* X, double* lam, double* xnorm, double* resid, int* iter, int* status, int* info);
 
 #ifdef __cplusplus
 }
