@@ -212,6 +212,10 @@ _sig("qr_gels_trust_wide_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_
 _sig("qr_lsacc_batched_solve_trust_dev", C.c_int, _vp, _vp, _ll, _vp, _ll, _vp, _ll, C.c_double, C.c_int, _vp, C.c_int, _ll, _vp, _vp, _vp, _vp,
      _vp, _vp)
 _sig("qr_lstsq_trust_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _ip)
+_sig("qr_gglse_batched_max_rows", C.c_int, C.c_int, C.c_int, C.c_int)
+_sig("qr_gglse_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp, C.c_int, _ll,
+     C.c_int, _vp, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _ll, _vp, C.c_int)
+_sig("qr_lstsq_constrained_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -754,6 +758,42 @@ def lstsq_trust_batched(A, b, delta, D=None, lam0=None, rtol=0.1, maxit=10):
     return X, lam, xnorm, resid, it[:batch].astype(np.int64), status[:batch].astype(np.int64), info[:batch].astype(np.int64)
 
 
+def gglse_batched_max_rows(n, p, nrhs):
+    """the most rows Plan.gglse_batched takes for p constraints on n unknowns and nrhs right-hand sides (qr_gglse_batched_max_rows; 0:
+    the shape is not taken at all; no device)"""
+    return lib.qr_gglse_batched_max_rows(int(n), int(p), int(nrhs))
+
+
+def lstsq_constrained_batched(A, C, b, d):
+    """min ||A_q x - b_q|| subject to C_q x = d_q for every member of A (batch, m, n), C (batch, p, n), b (batch, m, nrhs) and d (batch, p,
+    nrhs) through qr_lstsq_constrained_batched: returns (X, lam, resid, info) with X (batch, n, nrhs), the Lagrange multipliers lam
+    (batch, p, nrhs) of A^T (A x - b) + C^T lam = 0, resid[q, j] = ||A_q x_j - b_j|| and info[q] = 0, i + 1 for the smallest i with
+    R_c(i,i) == 0 exactly (a zero row of C_q) or p + i + 1 for the smallest i with R_a(i,i) == 0 exactly (X[q], lam[q] and resid[q] then
+    read 0; the other members are solved).  A singular member does not raise."""
+    At = _packed_batch(A, "lstsq_constrained_batched")
+    Ct = _packed_batch(C, "lstsq_constrained_batched")
+    bt = _packed_batch(b, "lstsq_constrained_batched")
+    dt = _packed_batch(d, "lstsq_constrained_batched")
+    batch, n, m = At.shape
+    p, nrhs = Ct.shape[2], bt.shape[1]
+    if Ct.shape[0] != batch or bt.shape[0] != batch or dt.shape[0] != batch:
+        raise QRError(f"lstsq_constrained_batched: A, C, b and d hold {batch}, {Ct.shape[0]}, {bt.shape[0]} and {dt.shape[0]} members", QR_E_ARG)
+    if Ct.shape[1] != n:
+        raise QRError(f"lstsq_constrained_batched: C has {Ct.shape[1]} columns, A has {n}", QR_E_ARG)
+    if bt.shape[2] != m or dt.shape[2] != p or dt.shape[1] != nrhs:
+        raise QRError(f"lstsq_constrained_batched: b must be ({batch}, {m}, nrhs) and d ({batch}, {p}, nrhs), got {bt.shape[::-1][:2]} and "
+                      f"{dt.shape[::-1][:2]} per member", QR_E_ARG)
+    X = np.empty((batch, nrhs, n))
+    lam = np.empty((batch, nrhs, p))
+    resid = np.empty((batch, nrhs))
+    info = np.zeros(max(batch, 1), dtype=np.intc)
+    rc = lib.qr_lstsq_constrained_batched(_p(At), m, n, _p(Ct), p, _p(bt), _p(dt), nrhs, batch, _p(X), _p(lam), _p(resid),
+                                          info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_constrained_batched")
+    return X.transpose(0, 2, 1), lam.transpose(0, 2, 1), resid, info[:batch].astype(np.int64)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -1123,6 +1163,15 @@ class Plan:
                                                  _dptr(dB), ldb, strideB, _dptr(ddelta), stridedelta, _dptr(dlam0), stridelam0, float(rtol),
                                                  int(maxit), _dptr(dX), ldx, strideX, _dptr(dlam), _dptr(dxnorm), _dptr(dresid), _dptr(diter),
                                                  _dptr(dstatus), _dptr(dinfo), batch), "qr_gels_trust_wide_batched_dev")
+
+    def gglse_batched(self, dA, m, n, lda, strideA, dC, p, ldc, strideC, dB, ldb, strideB, dD, ldd, strideD, nrhs, dX, ldx, strideX, dinfo, batch,
+                      dL=None, ldl=0, strideL=0, dresid=None, strideres=0):
+        """min ||A x - b|| subject to C x = d for `batch` members in one launch: dA (m x n), dC (p x n), dB (m x nrhs) and dD (p x nrhs) are
+        read only; x to dX (n x nrhs), the multipliers to dL (p x nrhs) and ||A x - b|| to dresid (nrhs per member) where given; dinfo:
+        one int per member (0, i + 1 for R_c(i,i) == 0, p + i + 1 for R_a(i,i) == 0: nothing else is written for that member)"""
+        check(lib.qr_gglse_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dC), p, ldc, strideC, _dptr(dB), ldb, strideB, _dptr(dD), ldd,
+                                       strideD, nrhs, _dptr(dX), ldx, strideX, _dptr(dL), ldl, strideL, _dptr(dresid), strideres,
+                                       _dptr(dinfo), batch), "qr_gglse_batched_dev")
 
     def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
         """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""

@@ -404,6 +404,28 @@ typedef struct qrd_bt_args {
 int qrd_bt_solve(void* stream, const qrd_bt_args* a);
 int qrd_bt_fused(void* stream, double* A, int m, int lda, size_t strideA, double* tau, size_t stridetau, double* B, const qrd_bt_args* a);
 
+/* batched equality-constrained least squares (qr_batched_lse.hip, called from qr_batched_lse.c only; mi355x_qr.h section 8h).  Per member
+ * min |A x - b| subject to C x = d by the null-space method: C^T = Q_c [R_c ; 0], R_c^T y1 = d, A~ = A Q_c, the QR of A~(:, p:n) with
+ * A~(:, 0:p) and b - A~(:, 0:p) y1 riding along, R_a y2 = the top of it, x = Q_c [y1 ; y2], resid from the tail, R_c lambda = g.
+ *   A: m x n (lda >= m), C: p x n (ldc >= p), B: m x nrhs, D: p x nrhs, none of them written; X: n x nrhs; L (p x nrhs) and resid (nrhs
+ *   per member, sres apart) may be NULL.  1 <= p <= n, m >= 1, m + p >= n, nrhs >= 1, n + nrhs <= QRD_B_MAX_N.
+ *   info[q]: 0; i + 1 for the smallest i with R_c(i,i) == 0; p + i + 1 for the smallest i with R_a(i,i) == 0; X, L and resid of such a
+ *   member are not written.
+ * qrd_bl_wave_route: m <= 64 and n + nrhs <= 32, one wave per member; else one workgroup per member, m <= qrd_bl_max_rows(n, p, nrhs):
+ * the largest m <= QRD_B_MAX_ROWS whose images fit 160 KiB of LDS (0: the shape is not taken at all).  qrd_bl_solve: one launch.
+ * batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_bl_args {
+    const double *A, *C, *B, *D;
+    double *X, *L, *resid;
+    int* info;
+    size_t sA, sC, sB, sD, sX, sL, sres;
+    int lda, ldc, ldb, ldd, ldx, ldl;
+    int m, n, p, nrhs, batch;
+} qrd_bl_args;
+int qrd_bl_wave_route(int m, int n, int nrhs);
+int qrd_bl_max_rows(int n, int p, int nrhs);
+int qrd_bl_solve(void* stream, const qrd_bl_args* a);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

@@ -51,6 +51,11 @@
  * and nlam values of lambda each (resident in HBM) go through one qr_gels_damped_batched_dev call: the time, and the worst forward error
  * ||x - x_s|| / ||x_s|| against nlam qr_gels_batched_dev solves of the stacked systems [A ; lambda I].
  *
+ * `./qr_device m n --batched count --lse p` does nothing else either: `count` seeded m x n matrices A, p x n constraint matrices C and one
+ * pair (b, d) each (resident in HBM) go through one qr_gglse_batched_dev call: the time, the worst ||C x - d|| / (||C|| ||x|| + ||d||), the
+ * worst KKT residual ||A^T (A x - b) + C^T lambda|| / (||A|| (||A|| ||x|| + ||b||) + ||C|| ||lambda||) (Frobenius norms, formed on the host)
+ * and the number of non-zero info words.
+ *
  * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
  * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
  * qr_lsacc_batched_slide_dev for the whole batch -- beside one qr_gels_batched_dev per window on copies of the windows: both wall times
@@ -983,9 +988,90 @@ static int batched_trust_main(int m, int n, int count, double frac)
     return 0;
 }
 
+/* count problems min |A x - b| subject to C x = d (A m x n, C p x n) through one qr_gglse_batched_dev call */
+static int batched_lse_main(int m, int n, int count, int p)
+{
+    if (count < 1 || p < 1 || qr_gglse_batched_max_rows(n, p, 1) < 1 || m < 1 || m < n - p || m > qr_gglse_batched_max_rows(n, p, 1)) {
+        fprintf(stderr, "--batched count --lse p needs count >= 1, 1 <= p <= n < %d, m + p >= n and 1 <= m <= qr_gglse_batched_max_rows(n, p, 1)\n",
+                QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d problems of %dx%d with %d constraints\n", count, m, n, p);
+    const size_t nc = (size_t) count, mn = (size_t) m * n, pn = (size_t) p * n;
+    const size_t tot = nc * (mn + pn + (size_t) m + (size_t) p), outs = nc * ((size_t) n + (size_t) p + 1);
+    double *H = malloc(sizeof(double) * tot), *O = malloc(sizeof(double) * outs);
+    int* info = malloc(sizeof(int) * nc);
+    if (!H || !O || !info) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t i = 0; i < tot; i++) H[i] = (double) rand() / RAND_MAX - 0.5;
+    const double *A = H, *C = A + nc * mn, *B = C + nc * pn, *D = B + nc * m;
+    qr_plan* plan = NULL;
+    double *dH = NULL, *dO = NULL;
+    int* di = NULL;
+    if (qr_plan_create(&plan, m > n ? m : n, n, 0, 0) || qr_device_malloc((void**) &dH, sizeof(double) * tot) ||
+        qr_device_malloc((void**) &dO, sizeof(double) * outs) || qr_device_malloc((void**) &di, sizeof(int) * nc) ||
+        qr_copy_to_device(dH, H, sizeof(double) * tot)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    const double *dA = dH, *dC = dA + nc * mn, *dB = dC + nc * pn, *dD = dB + nc * m;
+    double *dX = dO, *dL = dX + nc * n, *dres = dL + nc * p;
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {               /* (the inputs are read only: no copy between the trials) */
+        const double t0 = now();
+        int rc = qr_gglse_batched_dev(plan, dA, m, n, m, (long long) mn, dC, p, p, (long long) pn, dB, m, m, dD, p, p, 1, dX, n, n, dL, p, p, dres, 1, di,
+                                      count);
+        if (!rc) rc = qr_plan_sync(plan);
+        if (rc) { fprintf(stderr, "the batched call failed: %s\n", qr_strerror(rc)); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(O, dO, sizeof(double) * outs) || qr_copy_to_host(info, di, sizeof(int) * nc)) { fprintf(stderr, "copy back failed\n"); return 1; }
+    const double *X = O, *L = X + nc * n;
+    int failed = 0;
+    double wc = 0.0, wk = 0.0;
+    double* r = malloc(sizeof(double) * (size_t) m);
+    if (!r) { fprintf(stderr, "out of memory\n"); return 1; }
+    for (size_t q = 0; q < nc; q++) {
+        if (info[q]) { failed++; continue; }
+        const double *Aq = A + q * mn, *Cq = C + q * pn, *bq = B + q * m, *dq = D + q * p, *x = X + q * n, *l = L + q * p;
+        double nA = 0.0, nC = 0.0, nx = 0.0, nb = 0.0, nd = 0.0, nl = 0.0, ec = 0.0, ek = 0.0;
+        for (size_t i = 0; i < mn; i++) nA += Aq[i] * Aq[i];
+        for (size_t i = 0; i < pn; i++) nC += Cq[i] * Cq[i];
+        for (int i = 0; i < n; i++) nx += x[i] * x[i];
+        for (int i = 0; i < m; i++) nb += bq[i] * bq[i];
+        for (int i = 0; i < p; i++) { nd += dq[i] * dq[i]; nl += l[i] * l[i]; }
+        for (int i = 0; i < p; i++) {
+            double s = -dq[i];
+            for (int c = 0; c < n; c++) s += Cq[(size_t) c * p + i] * x[c];
+            ec += s * s;
+        }
+        for (int i = 0; i < m; i++) {
+            double s = -bq[i];
+            for (int c = 0; c < n; c++) s += Aq[(size_t) c * m + i] * x[c];
+            r[i] = s;
+        }
+        for (int c = 0; c < n; c++) {
+            double s = 0.0;
+            for (int i = 0; i < m; i++) s += Aq[(size_t) c * m + i] * r[i];
+            for (int i = 0; i < p; i++) s += Cq[(size_t) c * p + i] * l[i];
+            ek += s * s;
+        }
+        nA = sqrt(nA); nC = sqrt(nC);
+        const double c1 = sqrt(ec) / (nC * sqrt(nx) + sqrt(nd)), k1 = sqrt(ek) / (nA * (nA * sqrt(nx) + sqrt(nb)) + nC * sqrt(nl));
+        if (c1 > wc) wc = c1;
+        if (k1 > wk) wk = k1;
+    }
+    printf(" MMQR solved %d constrained %dx%d systems (p = %d) in %f s (avg over %d)   [batch resident in HBM]\n", count, m, n, p, el / TRIALS, TRIALS);
+    printf(" worst ||C x - d|| / (||C|| ||x|| + ||d||) = %.2e   worst KKT residual = %.2e   non-zero info words = %d\n", wc, wk, failed);
+    qr_device_free(dH); qr_device_free(dO); qr_device_free(di);
+    qr_plan_destroy(plan);
+    free(H); free(O); free(info); free(r);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -1014,6 +1100,9 @@ int main(int argc, char** argv)
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--trust") == 0)
                     return batched_trust_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atof(argv[k + 1]) : 0.5);
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--lse") == 0)
+                    return batched_lse_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atoi(argv[k + 1]) : 1);
             return batched_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
         }
     for (int i = 3; i < argc; i++)

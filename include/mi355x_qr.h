@@ -1127,6 +1127,68 @@ int qr_lstsq_trust_batched(const double* A, int m, int n, const double* b, int b
                            const double* D, const double* delta, const double* lam0, double rtol, int maxit,
                            double* X, double* lam, double* xnorm, double* resid, int* iter, int* status, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8h. Batched equality-constrained least squares: LAPACK dgglse's problem for every member of a batch,
+ *
+ *         min |A x - b|_2  subject to  C x = d,      A: m x n, C: p x n, 1 <= p <= n, m >= 1, m + p >= n,
+ *
+ * for nrhs >= 1 pairs (b, d), n + nrhs <= QR_BATCHED_MAX_N -- inverse kinematics with a contact constraint that must hold exactly, fits
+ * that interpolate given points or conserve a sum, the equality-constrained Gauss-Newton step inside the loops of 8f and 8g.  One launch
+ * whatever the batch size; nothing waits on the host.
+ *
+ * The method is the null-space method (Bjorck, Numerical Methods for Least Squares Problems, 5.1; Lawson & Hanson ch. 20):
+ *   1. C^T = Q_c [R_c ; 0] by Householder QR (section 8's column step on C read through the transposed index map).
+ *   2. R_c^T y1 = d.
+ *   3. A~ = A Q_c: every row of A takes the p reflectors from the right.
+ *   4. r = b - A~(:, 0:p) y1.
+ *   5. Householder QR of A~(:, p:n) with r and A~(:, 0:p) riding along; R_a y2 = (Q_a^T r)(0 : n-p).
+ *   6. x = Q_c [y1 ; y2].
+ *   7. resid = |(Q_a^T r)(n-p : m)|_2 = |A x - b|.
+ *   8. The Lagrange multipliers lambda of A^T (A x - b) + C^T lambda = 0: R_c lambda = g with
+ *      g_i = sum over rows >= n-p of (Q_a^T A~(:, 0:p))(row, i) (Q_a^T r)(row).
+ * p == n: x is fixed by the constraints, A only feeds resid and lambda.  m == n - p: resid is an exact 0.
+ *
+ * Section 8's conventions hold: member q lives at base + q * stride, column-major, strides count doubles; the plan supplies the stream
+ * only; batch == 0 returns 0 after the argument checks and launches nothing.  The four inputs are never written.
+ *
+ * dinfo[q]: 0; i + 1 for the smallest i < p with R_c(i,i) == 0 exactly (a zero row of C produces this); p + i + 1 for the smallest i with
+ * R_a(i,i) == 0 exactly.  Such a member is all or nothing: its X, L and resid are not written at all; the other members are unaffected
+ * and the call returns 0.  Dependence to rounding among the rows of C, or among the columns of A restricted to the null space of C, is
+ * NOT detected, as in sections 8 and 8e: the result is then as large and as wrong as the conditioning makes it.
+ *
+ * Routes, chosen from the shape alone.  m <= 64 and n + nrhs <= 32: one wave per member, four members per workgroup.  Otherwise one
+ * workgroup per member with [A~ | rhs] and the factors of C^T in LDS, for m <= qr_gglse_batched_max_rows(n, p, nrhs).  A member's results
+ * do not depend on the batch size or on its place in the batch, and repeated calls are bitwise equal.
+ *
+ * Out of scope: solving again from stored factors (the call returns none); p == 0 (qr_gels_batched_dev); rank-deficient C or [A ; C];
+ * inequality constraints; n + nrhs > QR_BATCHED_MAX_N; shapes that do not fit LDS; a single-matrix variant.
+ * ------------------------------------------------------------------------------------------- */
+
+/* the largest m taken for (n, p, nrhs) (at most 512); 0 if (n, p, nrhs) is not taken at all.  No device is touched. */
+int qr_gglse_batched_max_rows(int n, int p, int nrhs);
+
+/* dA: m x n (lda >= m, strideA >= lda * n); dC: p x n (ldc >= p, strideC >= ldc * n); dB: m x nrhs (ldb >= m, strideB >= ldb * nrhs);
+ * dD: p x nrhs (ldd >= p, strideD >= ldd * nrhs); dX: n x nrhs (ldx >= n, strideX >= ldx * nrhs); dL (may be NULL): the multipliers,
+ * p x nrhs (ldl >= p, strideL >= ldl * nrhs); dresid (may be NULL): nrhs per member, strideres >= nrhs apart; dinfo: one per member.
+ * QR_E_ARG, before any device is touched, for a shape or an operand outside these rules. */
+int qr_gglse_batched_dev(qr_plan* plan,
+                         const double* dA, int m, int n, int lda, long long strideA,
+                         const double* dC, int p, int ldc, long long strideC,
+                         const double* dB, int ldb, long long strideB,
+                         const double* dD, int ldd, long long strideD,
+                         int nrhs,
+                         double* dX, int ldx, long long strideX,
+                         double* dL, int ldl, long long strideL,
+                         double* dresid, long long strideres,
+                         int* dinfo, int batch);
+
+/* The same for a packed batch on host pointers (A: m x n, C: p x n, b: m x nrhs, d: p x nrhs per member, all untouched): X n x nrhs, L
+ * p x nrhs and resid nrhs per member (L and resid may be NULL), info one per member; X, L and resid of a member with an info word read 0.
+ * Returns QR_E_SINGULAR if any info word is non-zero.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_constrained_batched(const double* A, int m, int n, const double* C, int p,
+                                 const double* b, const double* d, int nrhs, int batch,
+                                 double* X, double* L, double* resid, int* info);
+
 #ifdef __cplusplus
 }
 #endif
