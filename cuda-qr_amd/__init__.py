@@ -216,6 +216,10 @@ _sig("qr_gglse_batched_max_rows", C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("qr_gglse_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, C.c_int, C.c_int, _ll, _vp, C.c_int, _ll, _vp, C.c_int, _ll,
      C.c_int, _vp, C.c_int, _ll, _vp, C.c_int, _ll, _vp, _ll, _vp, C.c_int)
 _sig("qr_lstsq_constrained_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _ip)
+_sig("qr_bvls_batched_max_rows", C.c_int, C.c_int)
+_sig("qr_bvls_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _vp, _ll, C.c_int, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp,
+     _vp, C.c_int)
+_sig("qr_lstsq_bounded_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _dp, _ip, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -794,6 +798,62 @@ def lstsq_constrained_batched(A, C, b, d):
     return X.transpose(0, 2, 1), lam.transpose(0, 2, 1), resid, info[:batch].astype(np.int64)
 
 
+def bvls_batched_max_rows(n):
+    """the most rows Plan.bvls_batched takes for n unknowns (qr_bvls_batched_max_rows; 0: n is not taken at all; no device)"""
+    return lib.qr_bvls_batched_max_rows(int(n))
+
+
+def _bound_batch(v, batch, n, what, name):
+    """None, (n,) or (batch, n) -> None or a C-contiguous (batch, n) array"""
+    if v is None:
+        return None
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape == (n,):
+        v = np.broadcast_to(v, (batch, n))
+    if v.shape != (batch, n):
+        raise QRError(f"{what}: {name} must be ({n},) or ({batch}, {n}), got {v.shape}", QR_E_ARG)
+    return np.ascontiguousarray(v)
+
+
+def lstsq_bounded_batched(A, b, lo=None, hi=None, maxit=0):
+    """min ||A_q x - b_q|| subject to lo <= x <= hi for every member of A (batch, m, n), m >= n, and b (batch, m) through
+    qr_lstsq_bounded_batched (bounded-variable least squares, the active-set loop of every member on the device).  lo, hi: None (that
+    side is unbounded), (n,) (shared by all members) or (batch, n); entries may be -inf / +inf.  maxit: the most eliminations per member
+    (<= 0: 3 n).  Returns (X, w, state, resid, iter, info): X (batch, n) with lo <= X <= hi exactly; w = A^T (b - A x); state -1 at lo,
+    0 free, +1 at hi; resid[q] = ||A_q x - b_q||; iter the eliminations taken; info 0, n + 1 at maxit (the last, feasible iterate is
+    returned), -1 for bounds that are no box and j + 1 for an exactly zero free column j (the other outputs of such a member read 0).  A
+    member with an info word does not raise."""
+    At = _packed_batch(A, "lstsq_bounded_batched")
+    batch, n, m = At.shape
+    b = np.asarray(b, dtype=np.float64)
+    if b.ndim == 3 and b.shape[2] == 1:
+        b = b[:, :, 0]
+    if b.shape != (batch, m):
+        raise QRError(f"lstsq_bounded_batched: b must be ({batch}, {m}), one right-hand side per member, got {b.shape}", QR_E_ARG)
+    b = np.ascontiguousarray(b)
+    lo = _bound_batch(lo, batch, n, "lstsq_bounded_batched", "lo")
+    hi = _bound_batch(hi, batch, n, "lstsq_bounded_batched", "hi")
+    X = np.empty((batch, n))
+    w = np.empty((batch, n))
+    resid = np.empty(batch)
+    state = np.zeros((max(batch, 1), n), dtype=np.intc)
+    it = np.zeros(max(batch, 1), dtype=np.intc)
+    info = np.zeros(max(batch, 1), dtype=np.intc)
+    rc = lib.qr_lstsq_bounded_batched(_p(At), m, n, _p(b), None if lo is None else _p(lo), None if hi is None else _p(hi), int(maxit), batch,
+                                      _p(X), _p(w), state.ctypes.data_as(_ip), _p(resid), it.ctypes.data_as(_ip), info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_bounded_batched")
+    return X, w, state[:batch].astype(np.int64), resid, it[:batch].astype(np.int64), info[:batch].astype(np.int64)
+
+
+def nnls_batched(A, b, maxit=0):
+    """non-negative least squares, min ||A_q x - b_q|| subject to x >= 0, for every member: lstsq_bounded_batched with lo = 0"""
+    A = np.asarray(A)
+    if A.ndim != 3:
+        raise QRError(f"nnls_batched: expected an array of shape (batch, rows, cols), got {A.shape}", QR_E_ARG)
+    return lstsq_bounded_batched(A, b, lo=np.zeros(A.shape[2]), hi=None, maxit=maxit)
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -1172,6 +1232,17 @@ class Plan:
         check(lib.qr_gglse_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dC), p, ldc, strideC, _dptr(dB), ldb, strideB, _dptr(dD), ldd,
                                        strideD, nrhs, _dptr(dX), ldx, strideX, _dptr(dL), ldl, strideL, _dptr(dresid), strideres,
                                        _dptr(dinfo), batch), "qr_gglse_batched_dev")
+
+    def bvls_batched(self, dA, m, n, lda, strideA, dB, strideB, dX, strideX, dinfo, batch, dlo=None, dhi=None, stridebnd=0, maxit=0, dW=None,
+                     strideW=0, dstate=None, stridestate=0, dresid=None, diter=None):
+        """min ||A x - b|| subject to lo <= x <= hi for `batch` members in one launch: dA (m x n, m >= n) and dB (m per member) are read
+        only; dlo / dhi (n per member, stridebnd apart, 0: shared; None: that side unbounded); x to dX (n per member), w = A^T (b - A x)
+        to dW, the states (int32: -1 at lo, 0 free, +1 at hi) to dstate, ||A x - b|| to dresid and the elimination count (int32) to diter
+        where given; maxit <= 0: 3 n; dinfo: one int32 per member (0; n + 1 at maxit, the feasible iterate written; -1 for bad bounds
+        and j + 1 for a zero free column j: nothing else is written for that member)"""
+        check(lib.qr_bvls_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dB), strideB, _dptr(dlo), _dptr(dhi), stridebnd, int(maxit),
+                                      _dptr(dX), strideX, _dptr(dW), strideW, _dptr(dstate), stridestate, _dptr(dresid), _dptr(diter),
+                                      _dptr(dinfo), batch), "qr_bvls_batched_dev")
 
     def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
         """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""

@@ -426,6 +426,29 @@ int qrd_bl_wave_route(int m, int n, int nrhs);
 int qrd_bl_max_rows(int n, int p, int nrhs);
 int qrd_bl_solve(void* stream, const qrd_bl_args* a);
 
+/* batched bound-constrained least squares (qr_batched_bvls.hip, called from qr_batched_bvls.c only; mi355x_qr.h section 8i).  Per member
+ * min |A x - b| subject to lo <= x <= hi by bounded-variable least squares: the active-set loop of every member runs inside one launch,
+ * every candidate a Householder QR of the free columns (in increasing index order, refilled from the untouched A) with r = b - A_B x_B
+ * riding along and one back substitution.
+ *   A: m x n (lda >= m, m >= n), B: m per member, neither written; lo, hi: n per member, sbnd apart (0: one vector for all members), each
+ *   may be NULL (all -inf / all +inf); X: n per member; W (n per member), state (n ints per member), resid and iter (one per member) may
+ *   be NULL.  maxit >= 1: the most eliminations per member.
+ *   info[q]: 0; -1 for bounds that are no box (lo > hi, a NaN, lo == +inf, hi == -inf); j + 1 for an exactly zero R(i,i) on free column j
+ *   (nothing but info is written for either); n + 1 at maxit eliminations (the last iterate, feasible, is written).
+ * qrd_bv_wave_route: m <= 64 and n + 1 <= 32, one wave per member; else one workgroup per member, m <= qrd_bv_max_rows(n): the largest
+ * m <= QRD_B_MAX_ROWS with 8 ((n + 1) qb_ld(m) + 6 n + 72) bytes within 160 KiB of LDS (0: n is not taken, n < 1 or n > 63).
+ * qrd_bv_solve: one launch.  batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_bv_args {
+    const double *A, *B, *lo, *hi;
+    double *X, *W, *resid;
+    int *state, *iter, *info;
+    size_t sA, sB, sbnd, sX, sW, sstate;
+    int lda, m, n, maxit, batch;
+} qrd_bv_args;
+int qrd_bv_wave_route(int m, int n);
+int qrd_bv_max_rows(int n);
+int qrd_bv_solve(void* stream, const qrd_bv_args* a);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

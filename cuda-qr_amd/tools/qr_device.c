@@ -56,6 +56,13 @@
  * worst KKT residual ||A^T (A x - b) + C^T lambda|| / (||A|| (||A|| ||x|| + ||b||) + ||C|| ||lambda||) (Frobenius norms, formed on the host)
  * and the number of non-zero info words.
  *
+ * `./qr_device m n --batched count --bvls` does nothing else either: `count` seeded planted problems min ||A x - b|| subject to
+ * lo <= x <= hi (resident in HBM) go through one qr_bvls_batched_dev call.  A member is planted on the host: about half its variables are
+ * drawn active, the residual r is a random vector made orthogonal to the free columns (Gram-Schmidt, twice), every active variable sits at
+ * lo where a_j^T r < 0 and at hi where it is > 0, b = A x* + r: x* and the state are then the unique solution.  Printed: the time, the worst
+ * stationarity measure max over free j of |a_j^T (b - A x)| / (||a_j|| (||A|| ||x|| + ||b||)) (Frobenius norms, formed on the host), the
+ * number of variables whose state is not the planted one (and of non-zero info words), the mean and the largest elimination count.
+ *
  * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
  * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
  * qr_lsacc_batched_slide_dev for the whole batch -- beside one qr_gels_batched_dev per window on copies of the windows: both wall times
@@ -1069,9 +1076,126 @@ static int batched_lse_main(int m, int n, int count, int p)
     return 0;
 }
 
+/* count planted problems min |A x - b| subject to lo <= x <= hi through one qr_bvls_batched_dev call */
+static int batched_bvls_main(int m, int n, int count)
+{
+    if (count < 1 || qr_bvls_batched_max_rows(n) < 1 || m < n || m > qr_bvls_batched_max_rows(n)) {
+        fprintf(stderr, "--batched count --bvls needs count >= 1, 1 <= n < %d and n <= m <= qr_bvls_batched_max_rows(n)\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d planted bound-constrained problems of %dx%d\n", count, m, n);
+    const size_t nc = (size_t) count, mn = (size_t) m * n;
+    const size_t tot = nc * (mn + (size_t) m + 2 * (size_t) n), outs = nc * (2 * (size_t) n + 1);
+    double *H = malloc(sizeof(double) * tot), *O = malloc(sizeof(double) * outs), *Qf = malloc(sizeof(double) * mn), *r = malloc(sizeof(double) * (size_t) m);
+    int *planted = malloc(sizeof(int) * nc * n), *IO = malloc(sizeof(int) * nc * ((size_t) n + 2));
+    if (!H || !O || !Qf || !r || !planted || !IO) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    double *A = H, *B = A + nc * mn, *LO = B + nc * m, *HI = LO + nc * n;
+    for (size_t q = 0; q < nc; q++) {
+        double *Aq = A + q * mn, *bq = B + q * m, *lo = LO + q * n, *hi = HI + q * n;
+        int* pl = planted + q * n;
+        for (size_t i = 0; i < mn; i++) Aq[i] = (double) rand() / RAND_MAX - 0.5;
+        for (int i = 0; i < m; i++) r[i] = (double) rand() / RAND_MAX - 0.5;
+        int nf = 0;
+        for (int j = 0; j < n; j++) {
+            lo[j] = -0.5 - (double) rand() / RAND_MAX;
+            hi[j] = 0.5 + (double) rand() / RAND_MAX;
+            pl[j] = rand() & 1;                       /* 1: active; the side is decided by the sign of a_j^T r below */
+            if (pl[j]) continue;
+            /* a free column: orthonormalised against the earlier free ones (twice), then r made orthogonal to it */
+            double* qc = Qf + (size_t) nf * m;
+            memcpy(qc, Aq + (size_t) j * m, sizeof(double) * (size_t) m);
+            for (int pass = 0; pass < 2; pass++)
+                for (int k = 0; k < nf; k++) {
+                    double d = 0.0;
+                    for (int i = 0; i < m; i++) d += Qf[(size_t) k * m + i] * qc[i];
+                    for (int i = 0; i < m; i++) qc[i] -= d * Qf[(size_t) k * m + i];
+                }
+            double nq = 0.0;
+            for (int i = 0; i < m; i++) nq += qc[i] * qc[i];
+            nq = sqrt(nq);
+            for (int i = 0; i < m; i++) qc[i] /= nq;
+            nf++;
+        }
+        for (int pass = 0; pass < 2; pass++)
+            for (int k = 0; k < nf; k++) {
+                double d = 0.0;
+                for (int i = 0; i < m; i++) d += Qf[(size_t) k * m + i] * r[i];
+                for (int i = 0; i < m; i++) r[i] -= d * Qf[(size_t) k * m + i];
+            }
+        memcpy(bq, r, sizeof(double) * (size_t) m);
+        for (int j = 0; j < n; j++) {
+            double xs = 0.8 * ((double) rand() / RAND_MAX - 0.5);
+            if (pl[j]) {
+                double g = 0.0;
+                for (int i = 0; i < m; i++) g += Aq[(size_t) j * m + i] * r[i];
+                pl[j] = g < 0.0 ? -1 : 1;
+                xs = g < 0.0 ? lo[j] : hi[j];
+            }
+            for (int i = 0; i < m; i++) bq[i] += Aq[(size_t) j * m + i] * xs;
+        }
+    }
+    qr_plan* plan = NULL;
+    double *dH = NULL, *dO = NULL;
+    int* dI = NULL;
+    if (qr_plan_create(&plan, m, n, 0, 0) || qr_device_malloc((void**) &dH, sizeof(double) * tot) ||
+        qr_device_malloc((void**) &dO, sizeof(double) * outs) || qr_device_malloc((void**) &dI, sizeof(int) * nc * ((size_t) n + 2)) ||
+        qr_copy_to_device(dH, H, sizeof(double) * tot)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    const double *dA = dH, *dB = dA + nc * mn, *dlo = dB + nc * m, *dhi = dlo + nc * n;
+    double *dX = dO, *dW = dX + nc * n, *dres = dW + nc * n;
+    int *dstate = dI, *diter = dstate + nc * n, *dinfo = diter + nc;
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {               /* (the inputs are read only: no copy between the trials) */
+        const double t0 = now();
+        int rc = qr_bvls_batched_dev(plan, dA, m, n, m, (long long) mn, dB, m, dlo, dhi, n, 0, dX, n, dW, n, dstate, n, dres, diter, dinfo, count);
+        if (!rc) rc = qr_plan_sync(plan);
+        if (rc) { fprintf(stderr, "the batched call failed: %s\n", qr_strerror(rc)); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(O, dO, sizeof(double) * outs) || qr_copy_to_host(IO, dI, sizeof(int) * nc * ((size_t) n + 2))) { fprintf(stderr, "copy back failed\n"); return 1; }
+    const double* X = O;
+    const int *state = IO, *iter = state + nc * n, *info = iter + nc;
+    int failed = 0, mismatched = 0, most = 0;
+    double worst = 0.0, iters = 0.0;
+    for (size_t q = 0; q < nc; q++) {
+        if (info[q]) { failed++; continue; }
+        const double *Aq = A + q * mn, *bq = B + q * m, *x = X + q * n;
+        double nA = 0.0, nx = 0.0, nb = 0.0;
+        for (size_t i = 0; i < mn; i++) nA += Aq[i] * Aq[i];
+        for (int i = 0; i < n; i++) nx += x[i] * x[i];
+        for (int i = 0; i < m; i++) nb += bq[i] * bq[i];
+        for (int i = 0; i < m; i++) {
+            double s = bq[i];
+            for (int c = 0; c < n; c++) s -= Aq[(size_t) c * m + i] * x[c];
+            r[i] = s;
+        }
+        const double nrm = sqrt(nA) * sqrt(nx) + sqrt(nb);
+        for (int c = 0; c < n; c++) {
+            if (state[q * n + c] != planted[q * n + c]) mismatched++;
+            if (state[q * n + c] != 0) continue;
+            double g = 0.0, na = 0.0;
+            for (int i = 0; i < m; i++) { g += Aq[(size_t) c * m + i] * r[i]; na += Aq[(size_t) c * m + i] * Aq[(size_t) c * m + i]; }
+            const double s1 = fabs(g) / (sqrt(na) * nrm);
+            if (s1 > worst) worst = s1;
+        }
+        iters += iter[q];
+        if (iter[q] > most) most = iter[q];
+    }
+    printf(" MMQR solved %d bound-constrained %dx%d systems in %f s (avg over %d)   [batch resident in HBM]\n", count, m, n, el / TRIALS, TRIALS);
+    printf(" worst free stationarity = %.2e   state mismatches = %d   non-zero info words = %d   eliminations: mean %.2f, most %d\n", worst, mismatched,
+           failed, failed < count ? iters / (count - failed) : 0.0, most);
+    qr_device_free(dH); qr_device_free(dO); qr_device_free(dI);
+    qr_plan_destroy(plan);
+    free(H); free(O); free(Qf); free(r); free(planted); free(IO);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -1100,6 +1224,8 @@ int main(int argc, char** argv)
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--trust") == 0)
                     return batched_trust_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atof(argv[k + 1]) : 0.5);
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--bvls") == 0) return batched_bvls_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--lse") == 0)
                     return batched_lse_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atoi(argv[k + 1]) : 1);

@@ -1189,6 +1189,80 @@ int qr_lstsq_constrained_batched(const double* A, int m, int n, const double* C,
                                  const double* b, const double* d, int nrhs, int batch,
                                  double* X, double* L, double* resid, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8i. Batched bound-constrained least squares: for every member of a batch
+ *
+ *         min |A x - b|_2  subject to  lo <= x <= hi,      A: m x n, m >= n, 1 <= n <= QR_BATCHED_MAX_N - 1, one b per member,
+ *
+ * each lo_j may be -inf and each hi_j +inf -- actuator and joint limits in the fits and control steps of 8 to 8h, non-negative
+ * abundances or concentrations (NNLS: lo = 0, hi = +inf), the box-constrained Gauss-Newton or Levenberg-Marquardt step.  Clipping an
+ * unconstrained solution is the wrong answer; an active-set loop on the host costs a launch, a copy and a host wait per change of the
+ * set.  Here the active-set loop of every member runs on the device: one launch whatever the batch size; nothing waits on the host.
+ *
+ * The method is bounded-variable least squares (Lawson & Hanson, Solving Least Squares Problems, ch. 23; Stark & Parker, BVLS).  The
+ * bound set holds the variables at a bound (state -1 at lo, +1 at hi), the free set F the rest (state 0).  Per member:
+ *   1. Start.  A variable with a finite lo starts at lo, otherwise at a finite hi; one with both bounds infinite is free from the start
+ *      and can never be bound.  x holds those bounds, 0 for the free ones.  The elimination count it = 0, no variable is banned.
+ *   2. Outer test (skipped on the first pass if a variable is free).  w = A^T (b - A x) from the untouched A.  Among the bound,
+ *      non-banned variables with lo_j < hi_j the largest of w_j (at lo) and -w_j (at hi), ties to the smallest index.  None > 0: done,
+ *      info 0.  Otherwise that variable t is freed.
+ *   3. Elimination.  it == maxit: done, info n + 1.  Otherwise ++it; r = b - A_B x_B; Householder QR of A(:, F), columns in increasing
+ *      index order, with r riding along; R z = (Q^T r)(0 : |F|).  An exactly zero R(i,i): info j + 1, j that column's index in A.
+ *   4. Anti-cycling, on the first elimination after t was freed: z_t on or outside the bound t left puts t back and bans it; go to 2.
+ *   5. Accept.  lo_F <= z <= hi_F: x_F = z, the bans are lifted, go to 2.
+ *   6. Blocked step.  alpha_j = (bound_j - x_j) / (z_j - x_j) over the free j with z_j outside a bound; the smallest, ties to the
+ *      smallest index k; x_F += alpha (z - x_F); x_k is set to its bound exactly and bound, and so is every other free variable that
+ *      now lies on or outside a bound.  Go to 3.
+ * Every candidate is factored from scratch from the untouched A.  it counts every elimination and it <= maxit is the only loop bound;
+ * maxit <= 0 means 3 n.  A comparison with a NaN is false and leads towards the count: no input makes a loop run longer.
+ *
+ * Section 8's conventions hold: member q lives at base + q * stride, column-major, strides count elements; the plan supplies the stream
+ * only; batch == 0 returns 0 after the argument checks and launches nothing.  A and b are never written.
+ *
+ * Outputs, with lo <= x <= hi holding exactly: x; state (-1 / 0 / +1 per variable); w = A^T (b - A x) recomputed from the untouched A at
+ * the returned x (w_j <= 0 at lo and >= 0 at hi up to rounding where info is 0, about 0 on the free ones); resid = |A x - b| formed
+ * from A and the returned x; iter, the elimination count.
+ *
+ * dinfo[q]: 0; -1 for bounds that are no box (lo_j > hi_j, a NaN bound, lo_j == +inf or hi_j == -inf) and j + 1 for an exactly zero
+ * R(i,i) on free column j: nothing but info is written for such a member; n + 1 at maxit eliminations: the outputs ARE written, the
+ * last iterate (feasible), its state, its w and resid -- a caller with a real-time budget takes it.  lo_j == hi_j is legal: state -1,
+ * never freed.  The other members are unaffected and the call returns 0.  Dependence to rounding among free columns is NOT detected.
+ *
+ * Routes, chosen from the shape alone.  m <= 64 and n + 1 <= 32: one wave per member, four members per workgroup.  Otherwise one
+ * workgroup per member with the image [A_F | r] in LDS, for m <= qr_bvls_batched_max_rows(n): the largest m <= 512 with
+ * 8 ((n + 1) ld(m) + 6 n + 72) bytes within 160 KiB, ld(m) the smallest value >= m that is 2 mod 32.  A member's results do not depend
+ * on the batch size or on its place in the batch, and repeated calls are bitwise equal.
+ *
+ * Out of scope: several right-hand sides per member; m < n; general linear inequalities, or bounds combined with 8h's equalities; a warm
+ * start from a given state; QR updating across changes of the free set; rank deficiency to rounding; a single-matrix variant; blocked
+ * or MFMA variants.
+ * ------------------------------------------------------------------------------------------- */
+
+/* the largest m taken for n unknowns (at most 512); 0 if n is not taken (n < 1 or n > QR_BATCHED_MAX_N - 1).  No device is touched. */
+int qr_bvls_batched_max_rows(int n);
+
+/* dA: m x n (lda >= m, strideA >= lda * n); dB: m per member (strideB >= m); dlo, dhi: n per member, stridebnd apart (0: one vector
+ * shared by all members, else >= n), either may be NULL: that side is unbounded; dX: n per member (strideX >= n); dW (may be NULL): n
+ * per member (strideW >= n); dstate (may be NULL): n ints per member (stridestate >= n); dresid, diter (may be NULL) and dinfo: one per
+ * member.  QR_E_ARG, before any device is touched, for a shape or an operand outside these rules (stridebnd is checked even when both
+ * bound pointers are NULL). */
+int qr_bvls_batched_dev(qr_plan* plan,
+                        const double* dA, int m, int n, int lda, long long strideA,
+                        const double* dB, long long strideB,
+                        const double* dlo, const double* dhi, long long stridebnd,
+                        int maxit,
+                        double* dX, long long strideX,
+                        double* dW, long long strideW,
+                        int* dstate, long long stridestate,
+                        double* dresid, int* diter,
+                        int* dinfo, int batch);
+
+/* The same for a packed batch on host pointers (A: m x n, b: m, lo and hi: n per member, either may be NULL, all untouched): X n, W n
+ * and state n per member, resid, iter and info one per member (W, state, resid and iter may be NULL); the outputs of a member with info
+ * -1 or j + 1 read 0.  Returns QR_E_SINGULAR if any info word is non-zero.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_bounded_batched(const double* A, int m, int n, const double* b, const double* lo, const double* hi,
+                             int maxit, int batch, double* X, double* W, int* state, double* resid, int* iter, int* info);
+
 #ifdef __cplusplus
 }
 #endif
