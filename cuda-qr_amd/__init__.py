@@ -260,6 +260,11 @@ if hasattr(lib, "qrd_gemm_tn_update_even"):        # (absent from libraries of e
          _vp, C.c_int, _vp, C.c_size_t, C.c_int)
     _sig("qrd_tn_even_launches", C.c_longlong)
     _sig("qrd_tn_even_last_grid", C.c_int)
+if hasattr(lib, "qrd_gemm_nn_tri"):        # (absent from libraries of earlier commits loaded for A/B runs through CUDA_QR_AMD_LIB)
+    _sig("qrd_gemm_nn_tri", C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int, C.c_double,
+         _vp, C.c_int)
+    _sig("qrd_gemm_nn_tri_tile", C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int)
+    _sig("qrd_vt_tri_launches", C.c_longlong)
 _sig("qrd_gemm_tn_dual", C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int,
      _vp, C.c_size_t)
 _sig("qrd_trsm_gt", C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int)

@@ -11,6 +11,15 @@ extern "C" {
 int qrd_init(void);
 int qrd_gemm_nn(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
                 int ldb, double beta, double* C, int ldc);
+/* C = A*B with B upper triangular (V*T): N = K <= 256, N > 32, alpha 1, beta 0 end the k loop of every column tile at the diagonal and
+ * never read B below row 128 (floor(j / 128) + 1) of column j; every other call is qrd_gemm_nn.  The same bits as qrd_gemm_nn for
+ * finite A (the skipped terms are a * 0, added last).  (qr_host.c holds a weak fallback for device layers without it.) */
+int qrd_gemm_nn_tri(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
+                    int ldb, double beta, double* C, int ldc);
+/* the same with the tile forced: 44, 22 or 11 (0: the built-in rule; -1: the generic kernel); kernel tests and A/Bs only */
+int qrd_gemm_nn_tri_tile(void* stream, int tile, int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C,
+                         int ldc);
+long long qrd_vt_tri_launches(void);        /* products that took the triangle-aware kernel so far in this process */
 int qrd_gemm_tn(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
                 int ldb, double beta, double* C, int ldc, double* slabs, size_t slab_cap, const double* Tm,
                 int ldt);

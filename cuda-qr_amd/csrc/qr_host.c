@@ -1024,6 +1024,15 @@ static int apply_vw(qr_plan* p, void* stream, const double* V, int ldv, int mk, 
     return qrd_gemm_nn(stream, mk, nc, kw, -1.0, V, ldv, Wbuf, kw, 1.0, A2, lda);
 }
 
+/* V*T with T upper triangular: the device layer (qr_kernels.hip) defines qrd_gemm_nn_tri, which ends each column tile's k loop at the
+ * diagonal.  This weak definition only stands where the host layer is linked against a device layer that has none (the stub builds of the
+ * sanitizer targets): the general product, which is the same result.  In the product and lab libraries the strong definition wins. */
+__attribute__((weak)) int qrd_gemm_nn_tri(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
+                                          int ldb, double beta, double* C, int ldc)
+{
+    return qrd_gemm_nn(stream, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+}
+
 /* Apply panel set e's block reflector to columns [c0, c0+nc):  A2 -= V (T^T (V^T A2)).
  * profile 1 = the wide update on the update stream: V*T is formed first when form_vt is set (class 3) and W = (V T)^T A2 is
  *             one long-K product (class 1), then A2 -= V W (class 0); kernels under their own profiler names;
@@ -1080,7 +1089,7 @@ static int update_cols_inner(qr_plan* p, void* stream, int e, double* dA, int ld
          * A2 -= V Wt^T are row-fast and go HBM -> LDS directly (qr_gemm_nt.hip) */
         if (form_vt || !p->vt_formed[e]) {     /* on demand: an earlier slice of this update may have taken the tall-skinny shortcut above */
             CHECK(prof_begin_on(p, 3, stream));
-            CHECK(qrd_gemm_nn(stream, mk, wout, wout, 1.0, p->Vw2[e], ldv, p->T2[e], p->ldt, 0.0, p->VT2[e], ldv));
+            CHECK(qrd_gemm_nn_tri(stream, mk, wout, wout, 1.0, p->Vw2[e], ldv, p->T2[e], p->ldt, 0.0, p->VT2[e], ldv));   /* T upper triangular */
             CHECK(prof_end(p, 2.0 * mk * (double) wout * wout, 16.0 * mk * wout));
             p->vt_formed[e] = 1;
         }
@@ -1101,7 +1110,7 @@ static int update_cols_inner(qr_plan* p, void* stream, int e, double* dA, int ld
         const int tagged = wout >= 128 && nc >= 128;
         if (form_vt || !p->vt_formed[e]) {     /* on demand: an earlier slice of this update may have taken the tall-skinny shortcut above */
             CHECK(prof_begin_on(p, 3, stream));
-            CHECK(qrd_gemm_nn(stream, mk, wout, wout, 1.0, p->Vw2[e], ldv, p->T2[e], p->ldt, 0.0, p->VT2[e], ldv));
+            CHECK(qrd_gemm_nn_tri(stream, mk, wout, wout, 1.0, p->Vw2[e], ldv, p->T2[e], p->ldt, 0.0, p->VT2[e], ldv));   /* T upper triangular */
             CHECK(prof_end(p, 2.0 * mk * (double) wout * wout, 16.0 * mk * wout));
             p->vt_formed[e] = 1;
         }
@@ -2497,10 +2506,17 @@ int qr_tsqr_factor_dev(qr_tsqr_plan* t, double* dA, int lda, double* dR)
     if (t->nranks > 1 && !t->comm) return QR_E_ARG;      /* plan made for an external transport: use local / exchange_buffers / stacked */
     if (t->nranks > 1 && t->pipe_ok && t->pipe_auto && t->pipe_calls == QR_TSQR_DECIDE_CALL) CHECK(tsqr_decide(t, 0));
     if (t->nranks > 1 && t->pipe_ok) return tsqr_factor_pipelined(t, dA, lda, dR, 0);
+    if (t->nranks == 1) {
+        /* one rank: the local factor IS the result, so R goes straight into the caller's array -- no pass through the send buffer (which
+         * this call therefore does not refresh) and no n x n copy out of it */
+        CHECK(qr_geqrf_dev(t->p, dA, t->m_local, t->n, lda, t->dtau));
+        CHECK(qr_extract_r_dev(t->p, dA, t->m_local, t->n, lda, dR, t->n, t->n));
+        t->local_done = 0;
+        return 0;
+    }
     CHECK(qr_tsqr_local_dev(t, dA, lda));
-    if (t->nranks > 1)
-        /* dRall is read by the copies of the previous step on this same stream: stream order is enough */
-        CHECK(qrd_allgather_f64(t->comm, t->p->s_main, t->dRp, t->dRall, (size_t) t->n * t->n));
+    /* dRall is read by the copies of the previous step on this same stream: stream order is enough */
+    CHECK(qrd_allgather_f64(t->comm, t->p->s_main, t->dRp, t->dRall, (size_t) t->n * t->n));
     return qr_tsqr_stacked_dev(t, dR);
 }
 

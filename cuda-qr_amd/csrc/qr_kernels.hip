@@ -30,10 +30,11 @@
 // C = beta*C + alpha*A*B     A: M x K (lda), B: K x N (ldb), C: M x N (ldc), all column-major.
 // Used for: trailing update A2 -= V*W (K = nb), VT = V*T, T merges, Q*R products, Q_local*Q_tree.
 // TAG only gives the wide trailing-update launches their own kernel name in profiler output (TAG = 1).
+// jb: the block's column tile; kend: where its k loop ends (K, or short of it where the rows of B from kend on are known zeros).
 template <int TI, int TJ, bool FAST>
 __device__ __forceinline__ void gemm_nn_body(int M, int N, int K, double alpha, const double* __restrict__ A, int lda,
                                              const double* __restrict__ B, int ldb, double beta,
-                                             double* __restrict__ C, int ldc)
+                                             double* __restrict__ C, int ldc, int jb, int kend)
 {
     constexpr int BM = 32 * TI, BN = 32 * TJ, LA = BM + 16;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -41,7 +42,7 @@ __device__ __forceinline__ void gemm_nn_body(int M, int N, int K, double alpha, 
     double* Bs = smem + 2 * BK * LA;        // [2][BN][LDKF]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wi = wave & 1, wj = wave >> 1;
-    const int i0 = blockIdx.x * BM, j0 = blockIdx.y * BN;
+    const int i0 = blockIdx.x * BM, j0 = jb * BN;
     const int l15 = lane & 15, l4 = lane >> 4;
 
     // beta == 1 with alpha = +-1 (the trailing update C -= V*W): C enters through the accumulators, acc = C/alpha
@@ -71,7 +72,7 @@ __device__ __forceinline__ void gemm_nn_body(int M, int N, int K, double alpha, 
     }
 
     // FAST (host-checked): every tile of this launch is fully in range, K % BK == 0, operands 16-B aligned
-    gemm_kloop<TI, TJ, true, FAST>(acc, A, lda, B, ldb, i0, j0, M, N, 0, K, As, Bs, tid, wi, wj, l15, l4);
+    gemm_kloop<TI, TJ, true, FAST>(acc, A, lda, B, ldb, i0, j0, M, N, 0, kend, As, Bs, tid, wi, wj, l15, l4);
 
     if (cinit || beta == 0.0) gemm_epilogue<TI, TJ, true>(acc, C, ldc, M, N, i0, j0, alpha, beta, wi, wj, l15, l4);
     else gemm_epilogue<TI, TJ, false>(acc, C, ldc, M, N, i0, j0, alpha, beta, wi, wj, l15, l4);
@@ -83,7 +84,22 @@ __global__ __launch_bounds__(256, 2) void gemm_nn_kernel(int M, int N, int K, do
                                                          const double* __restrict__ B, int ldb,
                                                          double beta, double* __restrict__ C, int ldc)
 {
-    gemm_nn_body<TI, TJ, FAST>(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+    gemm_nn_body<TI, TJ, FAST>(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, blockIdx.y, K);
+}
+
+// C = A*B with B upper triangular (V*T, N = K <= 256): the same tile body, but the k loop of the column tile [c0, c0 + BN) ends at
+// min(K, roundup(coff + c0 + BN, BK)) -- the rows of B below are zeros, so every output element is the same sum in the same order, and B is
+// never read below row 128 (floor(j / 128) + 1) of column j (BN divides 128).  coff: the launch's first column within B (the ragged right
+// strip is a launch of its own).  The tiles no longer carry equal work: blockIdx.y runs from the last (longest) column tile to the first,
+// so that no compute unit gets its long tile last.
+template <int TI, int TJ, bool FAST>
+__global__ __launch_bounds__(256, 2) void gemm_nn_tri_kernel(int M, int N, int K, const double* __restrict__ A, int lda,
+                                                             const double* __restrict__ B, int ldb, double* __restrict__ C, int ldc, int coff)
+{
+    constexpr int BN = 32 * TJ;
+    const int jb = (int) gridDim.y - 1 - (int) blockIdx.y;
+    const int kend = min(K, (coff + (jb + 1) * BN + BK - 1) / BK * BK);
+    gemm_nn_body<TI, TJ, FAST>(M, N, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, jb, kend);
 }
 
 // blockIdx.z = batch index: the same small product on operands a fixed stride apart (the T-merge tree)
@@ -94,7 +110,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nn_batch_kernel(int M, int N, int
                                                                double beta, double* __restrict__ C, int ldc, size_t sC)
 {
     const size_t z = blockIdx.z;
-    gemm_nn_body<TI, TJ, FAST>(M, N, K, alpha, A + z * sA, lda, B + z * sB, ldb, beta, C + z * sC, ldc);
+    gemm_nn_body<TI, TJ, FAST>(M, N, K, alpha, A + z * sA, lda, B + z * sB, ldb, beta, C + z * sC, ldc, blockIdx.y, K);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -538,6 +554,34 @@ __global__ void extract_r_kernel(const double* __restrict__ A, int lda, int m, i
     if (i < rrows && c < n) R[(size_t) c * ldr + i] = (i <= c && i < m) ? A[(size_t) c * lda + i] : 0.0;
 }
 
+// The same for 16-byte aligned A and R with even lda and ldr (host-checked): 16 bytes per lane, a workgroup writes rows [512 bx, 512 bx + 512)
+// of XR_COLS columns.  A workgroup wholly below the diagonal stores zeros and forms no load address.
+#define XR_COLS 8
+__global__ __launch_bounds__(256) void extract_r_v2_kernel(const double* __restrict__ A, int lda, int m, int n, double* __restrict__ R, int ldr, int rrows)
+{
+    const int i = 2 * (blockIdx.x * 256 + threadIdx.x), c0 = blockIdx.y * XR_COLS, c1 = min(n, c0 + XR_COLS);
+    if (i >= rrows) return;
+    const bool pair = i + 1 < rrows;
+    if ((int) blockIdx.x * 512 > c1 - 1) {       // block-uniform: every row of the block is below the diagonal of every column
+        for (int c = c0; c < c1; ++c) {
+            double* r = R + (size_t) c * ldr + i;
+            if (pair) *reinterpret_cast<v2d*>(r) = (v2d){0.0, 0.0}; else *r = 0.0;
+        }
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < XR_COLS; ++q) {
+        const int c = c0 + q;
+        if (c >= c1) break;
+        const double* a = A + (size_t) c * lda + i;
+        v2d v = (v2d){0.0, 0.0};
+        if (i + 1 <= c && i + 1 < m) v = *reinterpret_cast<const v2d*>(a);
+        else if (i <= c && i < m) v[0] = a[0];
+        double* r = R + (size_t) c * ldr + i;
+        if (pair) *reinterpret_cast<v2d*>(r) = v; else *r = v[0];
+    }
+}
+
 // block column [k, k + w) of R: out (rrows x w, ldr) = rows 0 .. k + j of column k + j of the factored matrix, zero below
 __global__ void extract_r_block_kernel(const double* __restrict__ A, int lda, int k, int w, double* __restrict__ R, int ldr, int rrows)
 {
@@ -719,6 +763,35 @@ static int launch_nn(hipStream_t s, int M, int N, int K, double alpha, const dou
     return rc;
 }
 
+// The triangle-aware product (gemm_nn_tri_kernel), split into interior and strips exactly as launch_nn splits the general one
+template <int TI, int TJ, bool FAST>
+static int launch_nn_tri1(hipStream_t s, int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc,
+                          int coff)
+{
+    constexpr int BM = 32 * TI, BN = 32 * TJ;
+    if (M <= 0 || N <= 0) return 0;
+    const size_t shm = sizeof(double) * (2 * BK * (BM + 16) + 2 * BN * LDKF);
+    dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN);
+    hipLaunchKernelGGL((gemm_nn_tri_kernel<TI, TJ, FAST>), grid, dim3(256), shm, s, M, N, K, A, lda, B, ldb, C, ldc, coff);
+    return (int) hipGetLastError();
+}
+
+template <int TI, int TJ>
+static int launch_nn_tri(hipStream_t s, int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc)
+{
+    constexpr int BM = 32 * TI, BN = 32 * TJ;
+    const bool al = vec_ok(A, lda) && vec_ok(B, ldb) && (K % BK) == 0;
+    const int Mi = al ? (M / BM) * BM : 0, Ni = al ? (N / BN) * BN : 0;
+    if (!(Mi > 0 && Ni > 0) || ((Mi < M || Ni < N) && (double) M * N * K < 4e8))
+        return launch_nn_tri1<TI, TJ, false>(s, M, N, K, A, lda, B, ldb, C, ldc, 0);
+    int rc = launch_nn_tri1<TI, TJ, true>(s, Mi, Ni, K, A, lda, B, ldb, C, ldc, 0);
+    if (!rc && Ni < N)      /* right strip: all rows, columns [Ni, N) */
+        rc = launch_nn_tri1<TI, TJ, false>(s, M, N - Ni, K, A, lda, B + (size_t) Ni * ldb, ldb, C + (size_t) Ni * ldc, ldc, Ni);
+    if (!rc && Mi < M)      /* bottom strip: rows [Mi, M), columns [0, Ni) */
+        rc = launch_nn_tri1<TI, TJ, false>(s, M - Mi, Ni, K, A + Mi, lda, B, ldb, C + Mi, ldc, 0);
+    return rc;
+}
+
 template <int TI, int TJ, bool FAST, int TAG = 0>
 static int launch_tn1(hipStream_t s, int M, int N, int K, int ksplit, int kchunk, double alpha, const double* A,
                       int lda, const double* B, int ldb, double beta, double* C, int ldc, size_t slab_stride)
@@ -877,6 +950,8 @@ int qrd_init(void)
     rc |= allow_lds(gemm_tn_kernel<4, 4, true, 4>, sizeof(double) * (4 * 128 * LDKF));
     rc |= allow_lds(gemm_tn_wide_kernel<1>, sizeof(double) * (2 * (128 + 256) * LDKF));
     rc |= allow_lds(gemm_nn_kernel<4, 4, false>, sizeof(double) * (2 * BK * (128 + 16) + 2 * 128 * LDKF));
+    rc |= allow_lds(gemm_nn_tri_kernel<4, 4, true>, sizeof(double) * (2 * BK * (128 + 16) + 2 * 128 * LDKF));
+    rc |= allow_lds(gemm_nn_tri_kernel<4, 4, false>, sizeof(double) * (2 * BK * (128 + 16) + 2 * 128 * LDKF));
     rc |= allow_lds(gemm_tn_kernel<4, 4, true>, sizeof(double) * (4 * 128 * LDKF));
     rc |= allow_lds(gemm_tn_kernel<4, 4, true, 0, true>, sizeof(double) * (4 * 128 * LDKF));
     rc |= allow_lds(gemm_tn_kernel<4, 4, true, 1, true>, sizeof(double) * (4 * 128 * LDKF));
@@ -935,6 +1010,22 @@ static int gemm_nn_update_impl(void* stream, int M, int N, int K, double alpha, 
     return rc;
 }
 
+// tile choice of the general product: big square tiles when the grid still fills the chip, smaller otherwise (TI TJ as two digits)
+static int nn_tile(int M, int N)
+{
+    const long long t44 = (long long) ((M + 127) / 128) * ((N + 127) / 128);
+    if (N > 64 && M > 64 && t44 >= 192) return 44;
+    if (N <= 32) return M >= 128 * 96 ? 41 : 11;
+    const long long t22 = (long long) ((M + 63) / 64) * ((N + 63) / 64);
+    return t22 >= 192 ? 22 : 11;
+}
+
+// tile of the triangle-aware product (N > 32, so never 41).  Measured on the update stream's 224 CUs at 2048 ... 16384 rows by 256 and 8192 by 128
+// (profiles/r23_vt_tri_r_direct.txt section 1): the 32 x 32 tile wins every row -- its k loops end within 32 rows of the diagonal (56 % of the
+// general product's multiply-adds at 256 columns; 62.5 % on 64-column tiles, 75 % on 128) and its many small workgroups even out what is left.
+// Taller products were not measured and keep the general product's tile.
+static int vt_tri_tile(int M, int N) { return M <= 16384 ? 11 : nn_tile(M, N); }
+
 int qrd_gemm_nn(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
                 int ldb, double beta, double* C, int ldc)
 {
@@ -945,20 +1036,36 @@ int qrd_gemm_nn(void* stream, int M, int N, int K, double alpha, const double* A
         return -1;
     }
     if (alpha == 0.0 && beta == 1.0) return 0;      // C unchanged (and no 0 * inf from the C/alpha shortcut)
-    // tile choice: big square tiles when the grid still fills the chip, smaller otherwise
-    const long long t44 = (long long) ((M + 127) / 128) * ((N + 127) / 128);
-    {
-        static const int tall_tile = 44;
-        if (tall_tile == 22 && M >= 65536 && N <= 512 && N > 32) return launch_nn<2, 2>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+    switch (nn_tile(M, N)) {
+    case 44: return launch_nn<4, 4>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+    case 41: return launch_nn<4, 1>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+    case 22: return launch_nn<2, 2>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+    default: return launch_nn<1, 1>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
     }
-    if (N > 64 && M > 64 && t44 >= 192) return launch_nn<4, 4>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-    if (N <= 32) {
-        if (M >= 128 * 96) return launch_nn<4, 1>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-        return launch_nn<1, 1>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-    }
-    const long long t22 = (long long) ((M + 63) / 64) * ((N + 63) / 64);
-    if (t22 >= 192) return launch_nn<2, 2>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-    return launch_nn<1, 1>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+}
+
+// V*T on the triangle (gemm_nn_tri_kernel); the tile by vt_tri_tile
+static std::atomic<long long> g_vt_tri_launches{0};
+long long qrd_vt_tri_launches(void) { return g_vt_tri_launches.load(); }
+
+int qrd_gemm_nn_tri_tile(void* stream, int tile, int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc)
+{
+    hipStream_t s = (hipStream_t) stream;
+    if (M <= 0 || N <= 0) return 0;
+    if (tile < 0 || N != K || N > 256 || N <= 32) return qrd_gemm_nn(stream, M, N, K, 1.0, A, lda, B, ldb, 0.0, C, ldc);
+    if (tile == 0) tile = vt_tri_tile(M, N);
+    if (tile != 44 && tile != 22 && tile != 11) return -1;
+    g_vt_tri_launches.fetch_add(1);
+    if (tile == 44) return launch_nn_tri<4, 4>(s, M, N, K, A, lda, B, ldb, C, ldc);
+    if (tile == 22) return launch_nn_tri<2, 2>(s, M, N, K, A, lda, B, ldb, C, ldc);
+    return launch_nn_tri<1, 1>(s, M, N, K, A, lda, B, ldb, C, ldc);
+}
+
+int qrd_gemm_nn_tri(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
+                    int ldb, double beta, double* C, int ldc)
+{
+    if (alpha != 1.0 || beta != 0.0) return qrd_gemm_nn(stream, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+    return qrd_gemm_nn_tri_tile(stream, 0, M, N, K, A, lda, B, ldb, C, ldc);
 }
 
 // C = alpha*A^T*B + beta*C with split-K through `slabs` (capacity slab_cap doubles).
@@ -1305,6 +1412,11 @@ int qrd_extract_v(void* stream, const double* P, int ld, int mk, int w, double* 
 
 int qrd_extract_r(void* stream, const double* A, int lda, int m, int n, double* R, int ldr, int rrows)
 {
+    if (vec_ok(A, lda) && vec_ok(R, ldr)) {
+        hipLaunchKernelGGL(extract_r_v2_kernel, dim3((rrows + 511) / 512, (n + XR_COLS - 1) / XR_COLS), dim3(256), 0, (hipStream_t) stream, A,
+                           lda, m, n, R, ldr, rrows);
+        return (int) hipGetLastError();
+    }
     hipLaunchKernelGGL(extract_r_kernel, dim3((rrows + 255) / 256, n), dim3(256), 0, (hipStream_t) stream, A, lda, m,
                        n, R, ldr, rrows);
     return (int) hipGetLastError();

@@ -129,7 +129,8 @@ int qr_thin_mgpu(const double* A, int m, int n, double* Q, double* R, int nb, in
  * once per full-width panel of a shard above 16384 rows for that panel's verdict word while its last pass still runs -- latch mode on
  * qr_tsqr_local_plan(tp) removes even that.  The stacked factorisation of one call overlaps the local factorisation
  * of the next (independent matrices).  qr_tsqr_sync() before results are read on another stream.  librccl.so is dlopen()ed
- * on first use.  nranks = 1 needs no id (NULL) and no communicator.  qr_tsqr_plan_create_comm takes an ncclComm_t the caller
+ * on first use.  nranks = 1 needs no id (NULL) and no communicator; there qr_tsqr_factor_dev writes R straight into dR and does NOT
+ * refresh the send buffer of qr_tsqr_exchange_buffers (qr_tsqr_local_dev does, at any rank count).  qr_tsqr_plan_create_comm takes an ncclComm_t the caller
  * already owns (as void*; NULL = the caller exchanges the factors itself: qr_tsqr_local_dev, copy through
  * qr_tsqr_exchange_buffers -- send: this rank's n*n doubles, recv: nranks*n*n in rank order --, qr_tsqr_stacked_dev). */
 typedef struct qr_tsqr_plan qr_tsqr_plan;
