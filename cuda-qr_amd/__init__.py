@@ -220,6 +220,12 @@ _sig("qr_bvls_batched_max_rows", C.c_int, C.c_int)
 _sig("qr_bvls_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _vp, _ll, C.c_int, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp,
      _vp, C.c_int)
 _sig("qr_lstsq_bounded_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _dp, _ip, _ip)
+_sig("qr_irls_batched_max_rows", C.c_int, C.c_int)
+_sig("qr_irls_batched_dev", C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _ll, C.c_double,
+     C.c_int, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, C.c_int)
+_sig("qr_gels_weighted_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, C.c_int)
+_sig("qr_lstsq_robust_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp,
+     _dp, _dp, _ip, _ip, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -859,6 +865,65 @@ def nnls_batched(A, b, maxit=0):
     return lstsq_bounded_batched(A, b, lo=np.zeros(A.shape[2]), hi=None, maxit=maxit)
 
 
+QR_LOSS_LS, QR_LOSS_HUBER, QR_LOSS_BISQUARE = 0, 1, 2
+_LOSSES = {"ls": QR_LOSS_LS, "huber": QR_LOSS_HUBER, "bisquare": QR_LOSS_BISQUARE}
+
+
+def irls_batched_max_rows(n):
+    """the most rows Plan.irls_batched takes for n unknowns (qr_irls_batched_max_rows; 0: n is not taken at all; no device)"""
+    return lib.qr_irls_batched_max_rows(int(n))
+
+
+def lstsq_robust_batched(A, b, loss="huber", tune=None, weights=None, scale=None, x0=None, tol=1e-8, maxit=0):
+    """A robust fit of every member of A (batch, m, n), m >= n, and b (batch, m) through qr_lstsq_robust_batched (iteratively reweighted
+    least squares, the reweighting loop of every member on the device).  loss: "huber", "bisquare" or "ls" (or a QR_LOSS_* value); tune:
+    the constant k or c (None: 1.345 / 4.685); weights: None, (m,) (shared by all members) or (batch, m) prior weights >= 0, a zero
+    masks the row; scale: None (the MAD scale of every iterate), a scalar or (batch,); x0: None or (batch, n), a warm start; tol: the
+    relative change of x that stops; maxit: the most solves per member (<= 0: 50).  Returns (X, w, scale, resid, iter, status, info): X
+    (batch, n); the robust weights w (batch, m); resid[q] = ||b_q - A_q x|| over the included rows; status 0 converged, 2 a zero scale,
+    3 maxit solves (the last iterate is returned); info 0, -1 for a bad weight or scale, -2 for fewer than n rows of positive weight,
+    i + 1 for an exactly zero R(i,i) (the other outputs of such a member read 0).  A member with an info word does not raise."""
+    At = _packed_batch(A, "lstsq_robust_batched")
+    batch, n, m = At.shape
+    b = np.asarray(b, dtype=np.float64)
+    if b.ndim == 3 and b.shape[2] == 1:
+        b = b[:, :, 0]
+    if b.shape != (batch, m):
+        raise QRError(f"lstsq_robust_batched: b must be ({batch}, {m}), one right-hand side per member, got {b.shape}", QR_E_ARG)
+    b = np.ascontiguousarray(b)
+    if isinstance(loss, str):
+        if loss not in _LOSSES:
+            raise QRError(f"lstsq_robust_batched: loss must be one of {sorted(_LOSSES)}, got {loss!r}", QR_E_ARG)
+        loss = _LOSSES[loss]
+    weights = _bound_batch(weights, batch, m, "lstsq_robust_batched", "weights")
+    x0 = _bound_batch(x0, batch, n, "lstsq_robust_batched", "x0")
+    if scale is not None:
+        scale = np.asarray(scale, dtype=np.float64)
+        if scale.ndim == 0:
+            scale = np.broadcast_to(scale, (batch,))
+        if scale.shape != (batch,):
+            raise QRError(f"lstsq_robust_batched: scale must be a scalar or ({batch},), got {scale.shape}", QR_E_ARG)
+        scale = np.ascontiguousarray(scale)
+    X = np.empty((batch, n))
+    w = np.empty((batch, m))
+    sc, resid = np.empty(batch), np.empty(batch)
+    it, status, info = (np.zeros(max(batch, 1), dtype=np.intc) for _ in range(3))
+    rc = lib.qr_lstsq_robust_batched(_p(At), m, n, _p(b), int(loss), 0.0 if tune is None else float(tune), None if weights is None else _p(weights),
+                                     None if scale is None else _p(scale), None if x0 is None else _p(x0), float(tol), int(maxit), batch,
+                                     _p(X), _p(w), _p(sc), _p(resid), it.ctypes.data_as(_ip), status.ctypes.data_as(_ip),
+                                     info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_robust_batched")
+    return X, w, sc, resid, it[:batch].astype(np.int64), status[:batch].astype(np.int64), info[:batch].astype(np.int64)
+
+
+def lstsq_weighted_batched(A, b, weights):
+    """weighted least squares, min sum_i weights_i (b_q - A_q x)_i^2, for every member: lstsq_robust_batched with the squared loss.
+    Returns (X, resid, info)."""
+    X, _, _, resid, _, _, info = lstsq_robust_batched(A, b, loss=QR_LOSS_LS, weights=weights)
+    return X, resid, info
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -1248,6 +1313,25 @@ class Plan:
         check(lib.qr_bvls_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dB), strideB, _dptr(dlo), _dptr(dhi), stridebnd, int(maxit),
                                       _dptr(dX), strideX, _dptr(dW), strideW, _dptr(dstate), stridestate, _dptr(dresid), _dptr(diter),
                                       _dptr(dinfo), batch), "qr_bvls_batched_dev")
+
+    def irls_batched(self, loss, dA, m, n, lda, strideA, dB, strideB, dX, strideX, dinfo, batch, tune=0.0, dprior=None, strideprior=0,
+                     dscale_in=None, dX0=None, strideX0=0, tol=1e-8, maxit=0, dW=None, strideW=0, dscale=None, dresid=None, diter=None,
+                     dstatus=None):
+        """weighted (loss 0), Huber (1) or bisquare (2) fits of `batch` members in one launch: dA (m x n, m >= n) and dB (m per member) are
+        read only; dprior (m per member, strideprior apart, 0: shared; None: ones; a zero masks the row); dscale_in (one per member; None:
+        the MAD scale); dX0 (n per member; None: a cold start); x to dX (n per member), the robust weights to dW (m per member), the scale
+        to dscale, ||b - A x|| to dresid, the solve count and the status (int32: 0 converged, 2 a zero scale, 3 maxit) to diter and
+        dstatus where given; tune <= 0: 1.345 / 4.685; maxit <= 0: 50; dinfo: one int32 per member (0; -1 for a bad weight or scale, -2
+        for fewer than n rows of positive weight, i + 1 for a zero R(i,i): nothing else is written for that member)"""
+        check(lib.qr_irls_batched_dev(self.h, int(loss), float(tune), _dptr(dA), m, n, lda, strideA, _dptr(dB), strideB, _dptr(dprior),
+                                      strideprior, _dptr(dscale_in), _dptr(dX0), strideX0, float(tol), int(maxit), _dptr(dX), strideX,
+                                      _dptr(dW), strideW, _dptr(dscale), _dptr(dresid), _dptr(diter), _dptr(dstatus), _dptr(dinfo), batch),
+              "qr_irls_batched_dev")
+
+    def gels_weighted_batched(self, dA, m, n, lda, strideA, dB, strideB, dprior, strideprior, dX, strideX, dinfo, batch, dresid=None):
+        """weighted least squares of `batch` members in one launch (qr_gels_weighted_batched_dev): irls_batched with the squared loss"""
+        check(lib.qr_gels_weighted_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dB), strideB, _dptr(dprior), strideprior, _dptr(dX),
+                                               strideX, _dptr(dresid), _dptr(dinfo), batch), "qr_gels_weighted_batched_dev")
 
     def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
         """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""

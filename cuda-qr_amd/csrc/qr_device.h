@@ -458,6 +458,31 @@ int qrd_bv_wave_route(int m, int n);
 int qrd_bv_max_rows(int n);
 int qrd_bv_solve(void* stream, const qrd_bv_args* a);
 
+/* batched robust and weighted least squares (qr_batched_irls.hip, called from qr_batched_irls.c only; mi355x_qr.h section 8j).  Per member
+ * iteratively reweighted least squares: the reweighting loop of every member runs inside one launch, every solve a Householder QR of the
+ * rows of [A | b] (refilled from the untouched inputs) times sqrt(prior_i w_i) and one back substitution.
+ *   A: m x n (lda >= m, m >= n), B: m per member, neither written; prior: m per member, sprior apart (0: one vector for all members),
+ *   NULL: ones; scale_in: one per member, NULL: the MAD scale of every iterate; X0: n per member, NULL: a cold start (not referenced for
+ *   loss 0); X: n per member; W (m per member), scale, resid, iter and status (one per member) may be NULL.  loss 0 / 1 / 2 (least
+ *   squares, Huber, bisquare), tune > 0 the tuning constant, tol >= 0, maxit >= 1: the most solves per member.
+ *   status[q]: 0 converged (or loss 0), 2 a zero scale, 3 maxit solves.  info[q]: 0; -1 for a prior weight that is negative, NaN or inf or
+ *   a scale_in that is no finite positive number; -2 for fewer than n rows of positive weight; i + 1 for an exactly zero R(i,i): nothing
+ *   but info is written for such a member.
+ * qrd_ir_wave_route: m <= 64 and n + 1 <= 32, one wave per member; else one workgroup per member, m <= qrd_ir_max_rows(n): the largest
+ * m <= QRD_B_MAX_ROWS with 8 ((n + 1) qb_ld(m) + 3 m + 2 n + 72) bytes within 160 KiB of LDS (0: n is not taken, n < 1 or n > 63).
+ * qrd_ir_solve: one launch.  batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_ir_args {
+    const double *A, *B, *prior, *scale_in, *X0;
+    double *X, *W, *scale, *resid;
+    int *iter, *status, *info;
+    size_t sA, sB, sprior, sX0, sX, sW;
+    double tune, tol;
+    int lda, m, n, loss, maxit, batch;
+} qrd_ir_args;
+int qrd_ir_wave_route(int m, int n);
+int qrd_ir_max_rows(int n);
+int qrd_ir_solve(void* stream, const qrd_ir_args* a);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

@@ -63,6 +63,11 @@
  * stationarity measure max over free j of |a_j^T (b - A x)| / (||a_j|| (||A|| ||x|| + ||b||)) (Frobenius norms, formed on the host), the
  * number of variables whose state is not the planted one (and of non-zero info words), the mean and the largest elimination count.
  *
+ * `./qr_device m n --batched count --robust frac` does nothing else either: `count` seeded planted problems b = A x* + 0.01 noise with a
+ * fraction `frac` of the rows shifted by +-[0.1, 0.5] (resident in HBM) go through one qr_irls_batched_dev call with the Huber loss and its
+ * defaults.  Printed: the time, the worst error ||x - x*|| / ||x*|| beside that of one qr_gels_batched_dev on copies of the same members,
+ * the mean and the largest solve count, and the number of non-zero info words.
+ *
  * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
  * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
  * qr_lsacc_batched_slide_dev for the whole batch -- beside one qr_gels_batched_dev per window on copies of the windows: both wall times
@@ -1193,9 +1198,94 @@ static int batched_bvls_main(int m, int n, int count)
     return 0;
 }
 
+/* count planted problems with a fraction frac of outlier rows through one qr_irls_batched_dev call (Huber), beside qr_gels_batched_dev */
+static int batched_robust_main(int m, int n, int count, double frac)
+{
+    if (count < 1 || qr_irls_batched_max_rows(n) < 1 || m < n || m > qr_irls_batched_max_rows(n) || !(frac >= 0.0 && frac < 0.5)) {
+        fprintf(stderr, "--batched count --robust frac needs count >= 1, 1 <= n < %d, n <= m <= qr_irls_batched_max_rows(n) and 0 <= frac < 0.5\n",
+                QR_BATCHED_MAX_N);
+        return 1;
+    }
+    const int nout = (int) (frac * m);
+    printf("Exact problem size: %d planted %dx%d problems with %d outlier rows each\n", count, m, n, nout);
+    const size_t nc = (size_t) count, mn = (size_t) m * n;
+    const size_t tot = nc * (mn + (size_t) m), outs = nc * (size_t) n;
+    double *H = malloc(sizeof(double) * tot), *XS = malloc(sizeof(double) * outs), *X = malloc(sizeof(double) * outs), *XG = malloc(sizeof(double) * nc * m);
+    int* IO = malloc(sizeof(int) * nc * 3);
+    if (!H || !XS || !X || !XG || !IO) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    double *A = H, *B = A + nc * mn;
+    for (size_t q = 0; q < nc; q++) {
+        double *Aq = A + q * mn, *bq = B + q * m, *xs = XS + q * n;
+        for (size_t i = 0; i < mn; i++) Aq[i] = (double) rand() / RAND_MAX - 0.5;
+        for (int j = 0; j < n; j++) xs[j] = 2.0 * ((double) rand() / RAND_MAX - 0.5);
+        for (int i = 0; i < m; i++) {
+            /* noise: the sum of twelve uniforms, variance 1, times 0.01 */
+            double g = -6.0;
+            for (int k = 0; k < 12; k++) g += (double) rand() / RAND_MAX;
+            double s = 0.01 * g;
+            for (int j = 0; j < n; j++) s += Aq[(size_t) j * m + i] * xs[j];
+            bq[i] = s;
+        }
+        for (int k = 0; k < nout; k++) {              /* every (m / nout)-th row, from a random offset */
+            const int i = (int) (((size_t) k * m) / nout + (size_t) (rand() % (m / nout))) % m;
+            const double sh = 0.1 + 0.4 * (double) rand() / RAND_MAX;
+            bq[i] += (rand() & 1) ? sh : -sh;
+        }
+    }
+    qr_plan* plan = NULL;
+    double *dH = NULL, *dG = NULL, *dX = NULL, *dtau = NULL;
+    int* dI = NULL;
+    if (qr_plan_create(&plan, m, n, 0, 0) || qr_device_malloc((void**) &dH, sizeof(double) * tot) || qr_device_malloc((void**) &dG, sizeof(double) * tot) ||
+        qr_device_malloc((void**) &dX, sizeof(double) * outs) || qr_device_malloc((void**) &dtau, sizeof(double) * outs) ||
+        qr_device_malloc((void**) &dI, sizeof(int) * nc * 3) || qr_copy_to_device(dH, H, sizeof(double) * tot) ||
+        qr_copy_to_device(dG, H, sizeof(double) * tot)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    const double *dA = dH, *dB = dA + nc * mn;
+    int *diter = dI, *dstatus = diter + nc, *dinfo = dstatus + nc;
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {               /* (the inputs are read only: no copy between the trials) */
+        const double t0 = now();
+        int rc = qr_irls_batched_dev(plan, QR_LOSS_HUBER, 0.0, dA, m, n, m, (long long) mn, dB, m, NULL, 0, NULL, NULL, 0, 1e-8, 0, dX, n, NULL, 0,
+                                     NULL, NULL, diter, dstatus, dinfo, count);
+        if (!rc) rc = qr_plan_sync(plan);
+        if (rc) { fprintf(stderr, "the batched call failed: %s\n", qr_strerror(rc)); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(X, dX, sizeof(double) * outs) || qr_copy_to_host(IO, dI, sizeof(int) * nc * 3)) { fprintf(stderr, "copy back failed\n"); return 1; }
+    /* the squared loss on copies of the same members (qr_gels_batched_dev factors in place) */
+    {
+        int rc = qr_gels_batched_dev(plan, dG, m, n, m, (long long) mn, dtau, n, dG + nc * mn, 1, m, m, dinfo, count);
+        if (!rc) rc = qr_plan_sync(plan);
+        if (rc || qr_copy_to_host(XG, dG + nc * mn, sizeof(double) * nc * m)) { fprintf(stderr, "the least-squares call failed\n"); return 1; }
+    }
+    const int *iter = IO, *info = IO + 2 * nc;
+    int failed = 0, most = 0;
+    double worst = 0.0, worst_ls = 0.0, iters = 0.0;
+    for (size_t q = 0; q < nc; q++) {
+        if (info[q]) { failed++; continue; }
+        const double *xs = XS + q * n, *x = X + q * n, *xg = XG + q * m;
+        double d = 0.0, dg = 0.0, nx = 0.0;
+        for (int j = 0; j < n; j++) { d += (x[j] - xs[j]) * (x[j] - xs[j]); dg += (xg[j] - xs[j]) * (xg[j] - xs[j]); nx += xs[j] * xs[j]; }
+        if (sqrt(d / nx) > worst) worst = sqrt(d / nx);
+        if (sqrt(dg / nx) > worst_ls) worst_ls = sqrt(dg / nx);
+        iters += iter[q];
+        if (iter[q] > most) most = iter[q];
+    }
+    printf(" MMQR solved %d robust (Huber) %dx%d systems in %f s (avg over %d)   [batch resident in HBM]\n", count, m, n, el / TRIALS, TRIALS);
+    printf(" worst ||x - x*|| / ||x*|| = %.2e (qr_gels_batched_dev: %.2e)   solves: mean %.2f, most %d   non-zero info words = %d\n", worst, worst_ls,
+           failed < count ? iters / (count - failed) : 0.0, most, failed);
+    qr_device_free(dH); qr_device_free(dG); qr_device_free(dX); qr_device_free(dtau); qr_device_free(dI);
+    qr_plan_destroy(plan);
+    free(H); free(XS); free(X); free(XG); free(IO);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --robust frac]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -1224,6 +1314,9 @@ int main(int argc, char** argv)
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--trust") == 0)
                     return batched_trust_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atof(argv[k + 1]) : 0.5);
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--robust") == 0)
+                    return batched_robust_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atof(argv[k + 1]) : 0.2);
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--bvls") == 0) return batched_bvls_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)

@@ -1264,6 +1264,97 @@ int qr_bvls_batched_dev(qr_plan* plan,
 int qr_lstsq_bounded_batched(const double* A, int m, int n, const double* b, const double* lo, const double* hi,
                              int maxit, int batch, double* X, double* W, int* state, double* resid, int* iter, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8j. Batched robust and weighted least squares: for every member of a batch
+ *
+ *         min  sum_i p_i rho((b - A x)_i / s),      A: m x n, m >= n, 1 <= n <= QR_BATCHED_MAX_N - 1, one b per member,
+ *
+ * with prior weights p_i >= 0 per observation (an inverse variance; p_i = 0 masks a missing sample or a saturated pixel without a
+ * different m per member) and rho the squared, the Huber or the Tukey bisquare loss -- the per-pixel fits, rolling regressions and
+ * calibrations of 8 to 8i when one bad sample must not move the answer.  The method is iteratively reweighted least squares with a MAD
+ * scale (Holland & Welsch 1977; MASS::rlm, statsmodels.RLM).  A host loop costs, per reweighting, a scaled copy of the batch, a
+ * launch, a residual pass, a median, a weight pass and a host wait, and runs as many rounds as the slowest member needs.  Here the loop of
+ * every member runs on the device: one launch whatever the batch size; nothing waits on the host.
+ *
+ * Per member:
+ *   1. Checks.  A p_i that is negative, NaN or inf, or a given scale that is not a finite positive number: info -1.  Rows with
+ *      p_i == 0 are excluded: they are read as exact zeros whatever they hold, so a NaN in such a row of A or b is harmless.
+ *   2. Start.  The robust weights w_i = 1, the solve count it = 0.  With dX0 (and a robust loss) x = X0 and step 4 comes first: a
+ *      bisquare fit started from a Huber fit.  Otherwise step 3.
+ *   3. Solve.  c_i = p_i w_i.  Fewer than n rows with c_i > 0: info -2.  it == maxit: status 3, done.  Otherwise ++it; row i of [A | b]
+ *      from the untouched inputs times sqrt(c_i); Householder QR with b riding along; R x = (Q^T b)(0 : n).  An exactly zero R(i,i):
+ *      info i + 1.
+ *   4. Residual, scale, weights.  r = b - A x from the untouched A.  QR_LOSS_LS: status 0, done.  s = the given scale, or
+ *      median{|r_i| : p_i > 0} / 0.6744897501960817 (an even count: half the sum of the two middle values).  s == 0 (more than half the
+ *      rows fitted exactly): status 2, w = 1, done.  u_i = |r_i| / s.  Huber: w_i = 1 if u_i <= k, else k / u_i.  Bisquare:
+ *      w_i = (1 - (u_i / c)^2)^2 if u_i < c, else 0.  tune <= 0: k = 1.345, c = 4.685.
+ *   5. Stopping test, once a solve has run and a previous x exists (X0 on a warm start; none after the first solve of a cold start):
+ *      max_j |x_j - xold_j| <= tol max_j |x_j|: status 0, done.  Otherwise go to 3.
+ * it counts solves and it <= maxit is the only loop bound; maxit <= 0 means 50.  A comparison with a NaN is false: a NaN in an included
+ * row turns every weight into a NaN and the member leaves at the next count with info -2.  No input makes a loop run longer.
+ *
+ * Section 8's conventions hold: member q lives at base + q * stride, column-major, strides count elements; the plan supplies the stream
+ * only; batch == 0 returns 0 after the argument checks and launches nothing.  A, b and the weights are never written.
+ *
+ * Outputs where info is 0: x; the robust weights w (m per member: those of the returned x's residuals, 1 for QR_LOSS_LS, for status 2
+ * and on excluded rows); the scale s (0 for QR_LOSS_LS); resid = |b - A x|_2 over the included rows, unweighted; it; status 0
+ * (converged, or QR_LOSS_LS), 2 (a zero scale) or 3 (maxit solves: x, w and s of the last iterate ARE written).
+ *
+ * dinfo[q]: 0; -1, -2 or i + 1 as above: nothing but info is written for such a member.  The other members are unaffected and the call
+ * returns 0.  Dependence to rounding among the columns is NOT detected.
+ *
+ * Routes, chosen from the shape alone.  m <= 64 and n + 1 <= 32: one wave per member, four members per workgroup.  Otherwise one
+ * workgroup per member with the image in LDS, for m <= qr_irls_batched_max_rows(n): the largest m <= 512 with
+ * 8 ((n + 1) ld(m) + 3 m + 2 n + 72) bytes within 160 KiB, ld(m) the smallest value >= m that is 2 mod 32.  A member's results do not
+ * depend on the batch size or on its place in the batch, and repeated calls are bitwise equal.  With QR_LOSS_LS and no weights x is
+ * bitwise qr_gels_batched_dev's.
+ *
+ * Out of scope: several right-hand sides per member; m < n; other losses (L1, Cauchy); Huber's proposal 2; leverage and covariance
+ * outputs; bounds or equalities combined with a robust loss; updating the factorisation between reweightings; a single-matrix variant;
+ * blocked or MFMA variants.
+ * ------------------------------------------------------------------------------------------- */
+#define QR_LOSS_LS 0          /* weighted least squares */
+#define QR_LOSS_HUBER 1       /* Huber loss */
+#define QR_LOSS_BISQUARE 2    /* Tukey bisquare loss */
+
+/* the largest m taken for n unknowns (at most 512); 0 if n is not taken (n < 1 or n > QR_BATCHED_MAX_N - 1).  No device is touched. */
+int qr_irls_batched_max_rows(int n);
+
+/* loss: QR_LOSS_*; tune: the constant k or c (<= 0: the default; NaN or inf: QR_E_ARG).  dA: m x n (lda >= m, strideA >= lda * n); dB: m
+ * per member (strideB >= m); dprior: m per member, strideprior apart (0: one vector shared by all members, else >= m), NULL: ones;
+ * dscale_in: one per member, NULL: the MAD scale; dX0: n per member (strideX0 >= n), NULL: a cold start (not referenced for QR_LOSS_LS);
+ * tol >= 0; dX: n per member (strideX >= n); dW (may be NULL): m per member (strideW >= m); dscale, dresid, diter, dstatus (may be
+ * NULL) and dinfo: one per member.  QR_E_ARG, before any device is touched, for a shape or an operand outside these rules (strideprior
+ * is checked even when dprior is NULL). */
+int qr_irls_batched_dev(qr_plan* plan, int loss, double tune,
+                        const double* dA, int m, int n, int lda, long long strideA,
+                        const double* dB, long long strideB,
+                        const double* dprior, long long strideprior,
+                        const double* dscale_in,
+                        const double* dX0, long long strideX0,
+                        double tol, int maxit,
+                        double* dX, long long strideX,
+                        double* dW, long long strideW,
+                        double* dscale, double* dresid, int* diter, int* dstatus,
+                        int* dinfo, int batch);
+
+/* Weighted least squares, min sum_i p_i (b - A x)_i^2: qr_irls_batched_dev with QR_LOSS_LS.  dresid (may be NULL): |b - A x|_2 over
+ * the rows with p_i > 0, unweighted. */
+int qr_gels_weighted_batched_dev(qr_plan* plan,
+                                 const double* dA, int m, int n, int lda, long long strideA,
+                                 const double* dB, long long strideB,
+                                 const double* dprior, long long strideprior,
+                                 double* dX, long long strideX,
+                                 double* dresid, int* dinfo, int batch);
+
+/* The same as qr_irls_batched_dev for a packed batch on host pointers (A: m x n, b: m, prior: m, scale_in: 1, x0: n per member; prior,
+ * scale_in and x0 may be NULL; all untouched): X n and W m per member, scale, resid, iter, status and info one per member (W, scale,
+ * resid, iter and status may be NULL); the outputs of a member with a non-zero info read 0.  Returns QR_E_SINGULAR if any info word is
+ * non-zero.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_robust_batched(const double* A, int m, int n, const double* b, int loss, double tune, const double* prior,
+                            const double* scale_in, const double* x0, double tol, int maxit, int batch,
+                            double* X, double* W, double* scale, double* resid, int* iter, int* status, int* info);
+
 #ifdef __cplusplus
 }
 #endif
