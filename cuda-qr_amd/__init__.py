@@ -226,6 +226,14 @@ _sig("qr_irls_batched_dev", C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int, C.c
 _sig("qr_gels_weighted_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, C.c_int)
 _sig("qr_lstsq_robust_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp,
      _dp, _dp, _ip, _ip, _ip)
+_sig("qr_stats_batched_max_rows", C.c_int, C.c_int)
+_sig("qr_covar_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _vp, _vp, C.c_int, _ll, _vp, _ll, _vp, C.c_int)
+_sig("qr_leverage_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _vp, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp,
+     C.c_int)
+_sig("qr_gels_stats_batched_dev", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll,
+     _vp, _vp, _vp, C.c_int, _ll, _vp, _ll, _vp, C.c_int)
+_sig("qr_lsacc_batched_covar_dev", C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _ll, _vp, _ll, _vp, _vp)
+_sig("qr_lstsq_stats_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip)
 _sig("qr_extract_r_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int)
 _sig("qr_gemm_dev", C.c_int, _vp, C.c_char, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int,
      C.c_double, _vp, C.c_int)
@@ -924,6 +932,44 @@ def lstsq_weighted_batched(A, b, weights):
     return X, resid, info
 
 
+QR_COV_UNSCALED, QR_COV_SCALED = 0, 1
+
+
+def stats_batched_max_rows(n):
+    """the most rows Plan.gels_stats_batched takes for n unknowns (qr_stats_batched_max_rows; 0: n is not taken at all; no device)"""
+    return lib.qr_stats_batched_max_rows(int(n))
+
+
+def lstsq_stats_batched(A, b, weights=None, scaled=True):
+    """The weighted least-squares fit of every member of A (batch, m, n), m >= n, and b (batch, m) with its statistics, through
+    qr_lstsq_stats_batched (one launch for the whole batch).  weights: None, (m,) (shared by all members) or (batch, m) prior weights
+    >= 0, a zero excludes the row; scaled: the covariance is sigma2 (A^T P A)^-1 (True) or (A^T P A)^-1 (False).  Returns a dict: x
+    (batch, n); resid (batch, m), b - A x with exact zeros on excluded rows; leverage (batch, m); sigma2 (batch,), sum p e^2 / dof; dof
+    (batch,); cov (batch, n, n); se (batch, n); info (batch,): 0, -1 for a bad weight, -2 for fewer than n rows of positive weight, -3
+    for scaled without a degree of freedom, i + 1 for an exactly zero R(i,i) (the other outputs of such a member read 0).  A member
+    with an info word does not raise."""
+    At = _packed_batch(A, "lstsq_stats_batched")
+    batch, n, m = At.shape
+    b = np.asarray(b, dtype=np.float64)
+    if b.ndim == 3 and b.shape[2] == 1:
+        b = b[:, :, 0]
+    if b.shape != (batch, m):
+        raise QRError(f"lstsq_stats_batched: b must be ({batch}, {m}), one right-hand side per member, got {b.shape}", QR_E_ARG)
+    b = np.ascontiguousarray(b)
+    weights = _bound_batch(weights, batch, m, "lstsq_stats_batched", "weights")
+    X, se = np.empty((batch, n)), np.empty((batch, n))
+    E, H = np.empty((batch, m)), np.empty((batch, m))
+    sig = np.empty(batch)
+    cov = np.empty((batch, n, n))
+    dof, info = (np.zeros(max(batch, 1), dtype=np.intc) for _ in range(2))
+    rc = lib.qr_lstsq_stats_batched(_p(At), m, n, _p(b), None if weights is None else _p(weights), QR_COV_SCALED if scaled else QR_COV_UNSCALED,
+                                    batch, _p(X), _p(E), _p(H), _p(sig), dof.ctypes.data_as(_ip), _p(cov), _p(se), info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_stats_batched")
+    return {"x": X, "resid": E, "leverage": H, "sigma2": sig, "dof": dof[:batch].astype(np.int64), "cov": cov, "se": se,
+            "info": info[:batch].astype(np.int64)}
+
+
 def tpqrt_max_rows():
     """the most rows one Plan.tpqrt / Plan.tpmqrt call takes (qr_tpqrt_max_rows)"""
     return lib.qr_tpqrt_max_rows()
@@ -1333,6 +1379,34 @@ class Plan:
         check(lib.qr_gels_weighted_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dB), strideB, _dptr(dprior), strideprior, _dptr(dX),
                                                strideX, _dptr(dresid), _dptr(dinfo), batch), "qr_gels_weighted_batched_dev")
 
+    def covar_batched(self, dR, n, ldr, strideR, dinfo, batch, dC=None, ldc=0, strideC=0, dse=None, stridese=0, djpvt=None, stridejpvt=0,
+                      drank=None, dmult=None):
+        """C = mult P [(R11^T R11)^-1 0; 0 0] P^T (to dC, n x n per member) and se = sqrt(diag C) (to dse, n per member) from the upper
+        triangle of dR (n x n per member; in-place factors may be passed as they are) in one launch; djpvt (int32, 0-based), drank (int32)
+        and dmult (one double per member) default to the identity, n and 1; dinfo: one int32 per member (0; i + 1 for a zero R(i,i); -1 for
+        a bad jpvt, rank or multiplier: nothing else is written for that member)"""
+        check(lib.qr_covar_batched_dev(self.h, _dptr(dR), n, ldr, strideR, _dptr(djpvt), stridejpvt, _dptr(drank), _dptr(dmult), _dptr(dC), ldc,
+                                       strideC, _dptr(dse), stridese, _dptr(dinfo), batch), "qr_covar_batched_dev")
+
+    def leverage_batched(self, dR, n, ldr, strideR, dA, mrows, lda, strideA, dH, strideH, dinfo, batch, dprior=None, strideprior=0, djpvt=None,
+                         stridejpvt=0, drank=None):
+        """dH[i] = p_i a_i^T (R^T R)^-1 a_i for the mrows rows of dA (the fitted rows or new points; read only) from the upper triangle of
+        dR in one launch; dprior (mrows per member, strideprior apart, 0: shared; None: ones; a zero excludes the row); dinfo: one int32
+        per member (0; i + 1 for a zero R(i,i); -1 for a bad jpvt, rank or weight)"""
+        check(lib.qr_leverage_batched_dev(self.h, _dptr(dR), n, ldr, strideR, _dptr(djpvt), stridejpvt, _dptr(drank), _dptr(dA), mrows, lda,
+                                          strideA, _dptr(dprior), strideprior, _dptr(dH), strideH, _dptr(dinfo), batch), "qr_leverage_batched_dev")
+
+    def gels_stats_batched(self, dA, m, n, lda, strideA, dB, strideB, dX, strideX, dinfo, batch, scaled=QR_COV_SCALED, dprior=None, strideprior=0,
+                           dE=None, strideE=0, dH=None, strideH=0, dsigma2=None, ddof=None, dC=None, ldc=0, strideC=0, dse=None, stridese=0):
+        """the weighted least-squares fit of `batch` members and its statistics in one launch (qr_gels_stats_batched_dev): dA (m x n) and
+        dB (m per member) are read only; x to dX, b - A x to dE, the leverages to dH (m per member), sum p e^2 / dof to dsigma2, dof
+        (int32) to ddof, the covariance (scaled by sigma2 where scaled) to dC and its standard errors to dse where given; dinfo: one int32
+        per member (0; -1 a bad weight, -2 fewer than n rows of positive weight, -3 scaled without a degree of freedom, i + 1 a zero
+        R(i,i): nothing else is written for that member)"""
+        check(lib.qr_gels_stats_batched_dev(self.h, int(scaled), _dptr(dA), m, n, lda, strideA, _dptr(dB), strideB, _dptr(dprior), strideprior,
+                                            _dptr(dX), strideX, _dptr(dE), strideE, _dptr(dH), strideH, _dptr(dsigma2), _dptr(ddof), _dptr(dC), ldc,
+                                            strideC, _dptr(dse), stridese, _dptr(dinfo), batch), "qr_gels_stats_batched_dev")
+
     def geqrf_batched(self, dA, m, n, lda, strideA, dtau, stridetau, batch):
         """dgeqr2 of `batch` small matrices in place (matrix q at dA + q strideA doubles), tau to dtau + q stridetau"""
         check(lib.qr_geqrf_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dtau), stridetau, batch), "qr_geqrf_batched_dev")
@@ -1607,6 +1681,13 @@ class LsAccumulatorBatched:
         check(lib.qr_lsacc_batched_solve_trust_dev(self.h, _dptr(dD), strideD, _dptr(ddelta), stridedelta, _dptr(dlam0), stridelam0, float(rtol),
                                                    int(maxit), _dptr(dX), ldx, strideX, _dptr(dlam), _dptr(dxnorm), _dptr(dresid), _dptr(diter),
                                                    _dptr(dstatus), _dptr(dinfo)), "qr_lsacc_batched_solve_trust_dev")
+
+    def covar(self, dinfo, scaled=QR_COV_SCALED, rhs=0, dC=None, ldc=0, strideC=0, dse=None, stridese=0, dsigma2=None):
+        """the covariance (dC, n x n per member) and standard errors (dse) of every member from the state, which stays untouched:
+        (R^T R)^-1, times sigma2 = rss[rhs] / (rows - n) where scaled; sigma2 to dsigma2; dinfo: 0, i + 1 for a member that holds fewer
+        than n rows, -3 for scaled with rows == n"""
+        check(lib.qr_lsacc_batched_covar_dev(self.h, int(scaled), int(rhs), _dptr(dC), ldc, strideC, _dptr(dse), stridese, _dptr(dsigma2),
+                                             _dptr(dinfo)), "qr_lsacc_batched_covar_dev")
 
     def reset(self):
         check(lib.qr_lsacc_batched_reset(self.h), "qr_lsacc_batched_reset")

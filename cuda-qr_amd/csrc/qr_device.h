@@ -483,6 +483,56 @@ int qrd_ir_wave_route(int m, int n);
 int qrd_ir_max_rows(int n);
 int qrd_ir_solve(void* stream, const qrd_ir_args* a);
 
+/* batched covariance, standard errors and leverages (qr_batched_stats.hip, called from qr_batched_stats.c only; mi355x_qr.h section 8k).
+ * qrd_bs_covar: per member C = mult P [(R11^T R11)^-1 0; 0 0] P^T from the upper triangle of R (n x n, ldr >= n, n <= QRD_B_MAX_N; the
+ *   strict lower triangle is not read), R11 its leading rank x rank block, through T = R11^-1 and T T^T.  jpvt (n per member, sj apart),
+ *   rank and mult (one per member) may be NULL: the identity, n and 1.  C (n x n, ldc >= n) and se (n per member) may be NULL, not both.
+ *   acc != 0 (the batched accumulator): mult is formed on the device, sigma2 = rss[q nrhs + rhs] / (rows[q] - n) (+inf when rows == n),
+ *   written to sigma2 where given, and used as the multiplier where scaled != 0.
+ *   info[q]: 0; -1 for a jpvt that is no permutation, a rank outside 0 .. n or a multiplier that is negative, NaN or inf; i + 1 for the
+ *   smallest i < rank with R(i,i) == 0; -3 (acc) for scaled with rows == n (acc and scaled: -1 also for a sigma2 that is NaN or inf).  One launch: a wave per member for n <= 32
+ *   (qrd_bs_cov_wave_route), else a workgroup per member.
+ * qrd_bs_leverage: H[i] = prior_i |R11^-T (P^T a_i)(0 : rank)|^2 for the mrows rows of A (mrows x n, lda >= mrows, any mrows >= 1, not
+ *   written); prior as in qrd_ir_args; info -1 also for a prior weight that is negative, NaN or inf.  One launch of batch x nchunk
+ *   workgroups, nchunk = qrd_bs_lev_chunks(mrows): 256 rows each, one per thread.
+ * qrd_bs_fit: the weighted least-squares fit of qrd_ir_solve at loss 0 with its statistics in one launch: X (n), E (m: b - A x, 0 on
+ *   excluded rows), H (m: the leverages), sigma2 = sum p e^2 / dof, dof = (rows with p > 0) - n, C and se as qrd_bs_covar computes them
+ *   from the fit's R with the multiplier 1 (scaled == 0) or sigma2 (scaled != 0); everything but X and info may be NULL.  info[q]: 0; -1
+ *   a bad prior weight; -2 fewer than n rows with p > 0; -3 scaled with dof == 0; i + 1 an exactly zero R(i,i).
+ *   qrd_bs_fit_wave_route: m <= 64 and n + 1 <= 32, one wave per member; else one workgroup per member, m <= qrd_bs_max_rows(n): the
+ *   largest m <= QRD_B_MAX_ROWS with 8 ((n + 1) qb_ld(m) + n + 72) bytes within 160 KiB of LDS (0: n is not taken, n < 1 or n > 63).
+ * On a non-zero info word nothing else is written for that member.  batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_bs_args {
+    const double *R, *mult, *rss;
+    const int *jpvt, *rank, *rows;
+    double *C, *se, *sigma2;
+    int* info;
+    size_t sR, sj, sC, sse;
+    int ldr, ldc, n, batch, acc, scaled, nrhs, rhs;
+} qrd_bs_args;
+typedef struct qrd_bs_lev_args {
+    const double *R, *A, *prior;
+    const int *jpvt, *rank;
+    double* H;
+    int* info;
+    size_t sR, sj, sA, sprior, sH;
+    int ldr, lda, n, mrows, nchunk, batch;
+} qrd_bs_lev_args;
+typedef struct qrd_bs_fit_args {
+    const double *A, *B, *prior;
+    double *X, *E, *H, *sigma2, *C, *se;
+    int *dof, *info;
+    size_t sA, sB, sprior, sX, sE, sH, sC, sse;
+    int lda, ldc, m, n, scaled, batch;
+} qrd_bs_fit_args;
+int qrd_bs_cov_wave_route(int n);
+int qrd_bs_fit_wave_route(int m, int n);
+int qrd_bs_max_rows(int n);
+int qrd_bs_lev_chunks(int mrows);
+int qrd_bs_covar(void* stream, const qrd_bs_args* a);
+int qrd_bs_leverage(void* stream, const qrd_bs_lev_args* a);
+int qrd_bs_fit(void* stream, const qrd_bs_fit_args* a);
+
 #define QRD_LEAFW 32
 
 #ifdef __cplusplus

@@ -68,6 +68,10 @@
  * defaults.  Printed: the time, the worst error ||x - x*|| / ||x*|| beside that of one qr_gels_batched_dev on copies of the same members,
  * the mean and the largest solve count, and the number of non-zero info words.
  *
+ * `./qr_device m n --batched count --stats` does nothing else either: `count` seeded members b = A x* + 0.01 noise (resident in HBM) go
+ * through one qr_gels_stats_batched_dev call with every output (QR_COV_UNSCALED, no weights).  Printed: the time, the worst |sum h - n|,
+ * the worst ||C A^T A - I||_F (formed on the host), and the number of non-zero info words.
+ *
  * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
  * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
  * qr_lsacc_batched_slide_dev for the whole batch -- beside one qr_gels_batched_dev per window on copies of the windows: both wall times
@@ -1283,9 +1287,89 @@ static int batched_robust_main(int m, int n, int count, double frac)
     return 0;
 }
 
+/* count seeded members through one qr_gels_stats_batched_dev call with every output */
+static int batched_stats_main(int m, int n, int count)
+{
+    if (count < 1 || qr_stats_batched_max_rows(n) < 1 || m < n || m > qr_stats_batched_max_rows(n)) {
+        fprintf(stderr, "--batched count --stats needs count >= 1, 1 <= n < %d and n <= m <= qr_stats_batched_max_rows(n)\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    printf("Exact problem size: %d seeded %dx%d fits with residuals, leverages, covariance and standard errors\n", count, m, n);
+    const size_t nc = (size_t) count, mn = (size_t) m * n, nn = (size_t) n * n;
+    const size_t ins = nc * (mn + (size_t) m), outs = nc * ((size_t) n + 2 * (size_t) m + 1 + nn + (size_t) n);
+    double *H = malloc(sizeof(double) * ins), *O = malloc(sizeof(double) * outs);
+    int* IO = malloc(sizeof(int) * nc * 2);
+    if (!H || !O || !IO) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    double *A = H, *B = A + nc * mn;
+    for (size_t q = 0; q < nc; q++) {
+        double *Aq = A + q * mn, *bq = B + q * m;
+        for (size_t i = 0; i < mn; i++) Aq[i] = (double) rand() / RAND_MAX - 0.5;
+        for (int i = 0; i < m; i++) bq[i] = 0.01 * ((double) rand() / RAND_MAX - 0.5);
+        for (int j = 0; j < n; j++) {
+            const double xs = 2.0 * ((double) rand() / RAND_MAX - 0.5);
+            for (int i = 0; i < m; i++) bq[i] += Aq[(size_t) j * m + i] * xs;
+        }
+    }
+    qr_plan* plan = NULL;
+    double *dH = NULL, *dO = NULL;
+    int* dI = NULL;
+    if (qr_plan_create(&plan, m, n, 0, 0) || qr_device_malloc((void**) &dH, sizeof(double) * ins) || qr_device_malloc((void**) &dO, sizeof(double) * outs) ||
+        qr_device_malloc((void**) &dI, sizeof(int) * nc * 2) || qr_copy_to_device(dH, H, sizeof(double) * ins)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    const double *dA = dH, *dB = dA + nc * mn;
+    double *dX = dO, *dE = dX + nc * n, *dLev = dE + nc * m, *dsig = dLev + nc * m, *dC = dsig + nc, *dse = dC + nc * nn;
+    int *ddof = dI, *dinfo = dI + nc;
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {               /* (the inputs are read only: no copy between the trials) */
+        const double t0 = now();
+        int rc = qr_gels_stats_batched_dev(plan, QR_COV_UNSCALED, dA, m, n, m, (long long) mn, dB, m, NULL, 0, dX, n, dE, m, dLev, m, dsig, ddof, dC,
+                                           n, (long long) nn, dse, n, dinfo, count);
+        if (!rc) rc = qr_plan_sync(plan);
+        if (rc) { fprintf(stderr, "the batched call failed: %s\n", qr_strerror(rc)); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(O, dO, sizeof(double) * outs) || qr_copy_to_host(IO, dI, sizeof(int) * nc * 2)) { fprintf(stderr, "copy back failed\n"); return 1; }
+    const double *Lev = O + nc * n + nc * m, *Cv = Lev + nc * m + nc;
+    const int* info = IO + nc;
+    int failed = 0;
+    double worst_h = 0.0, worst_c = 0.0;
+    double* G = malloc(sizeof(double) * nn);
+    if (!G) { fprintf(stderr, "out of memory\n"); return 1; }
+    for (size_t q = 0; q < nc; q++) {
+        if (info[q]) { failed++; continue; }
+        const double *Aq = A + q * mn, *Cq = Cv + q * nn, *hq = Lev + q * m;
+        double sh = 0.0;
+        for (int i = 0; i < m; i++) sh += hq[i];
+        if (fabs(sh - n) > worst_h) worst_h = fabs(sh - n);
+        for (int a = 0; a < n; a++)
+            for (int c = 0; c < n; c++) {
+                double s = 0.0;
+                for (int i = 0; i < m; i++) s += Aq[(size_t) a * m + i] * Aq[(size_t) c * m + i];
+                G[(size_t) c * n + a] = s;
+            }
+        double f = 0.0;
+        for (int a = 0; a < n; a++)
+            for (int c = 0; c < n; c++) {
+                double s = a == c ? -1.0 : 0.0;
+                for (int k = 0; k < n; k++) s += Cq[(size_t) k * n + a] * G[(size_t) c * n + k];
+                f += s * s;
+            }
+        if (sqrt(f) > worst_c) worst_c = sqrt(f);
+    }
+    printf(" MMQR fitted %d %dx%d systems with statistics in %f s (avg over %d)   [batch resident in HBM]\n", count, m, n, el / TRIALS, TRIALS);
+    printf(" worst |sum h - n| = %.2e   worst ||C A^T A - I|| = %.2e   non-zero info words = %d\n", worst_h, worst_c, failed);
+    qr_device_free(dH); qr_device_free(dO); qr_device_free(dI);
+    qr_plan_destroy(plan);
+    free(G); free(H); free(O); free(IO);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --robust frac]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --robust frac | --stats]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -1317,6 +1401,8 @@ int main(int argc, char** argv)
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--robust") == 0)
                     return batched_robust_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atof(argv[k + 1]) : 0.2);
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--stats") == 0) return batched_stats_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--bvls") == 0) return batched_bvls_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)

@@ -1355,6 +1355,110 @@ int qr_lstsq_robust_batched(const double* A, int m, int n, const double* b, int 
                             const double* scale_in, const double* x0, double tol, int maxit, int batch,
                             double* X, double* W, double* scale, double* resid, int* iter, int* status, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8k. Batched covariance, standard errors and leverages: what says how good the fits of 8 to 8j are.  For the weighted problem of 8j
+ * (P = diag(p)) the calls give the parameter covariance sigma2 (A^T P A)^-1 and its standard errors, the residuals and the variance
+ * estimate sigma2 = sum_i p_i e_i^2 / dof, the leverages h_i = p_i a_i^T (A^T P A)^-1 a_i, and the same quadratic form for new points
+ * (the prediction variance).  MINPACK ships covar beside qrsolv and lmpar (8f, 8g); this is covar for a batch.
+ *
+ * Everything is computed from the triangle R of a QR factorisation, A^T P A = R^T R (with column pivoting: of A P_c), and R^T R is
+ * never formed: the errors are of order kappa(A) eps, not kappa^2.  With r the rank and R11 the leading r x r block:
+ *   T = R11^-1   along the rows, T R11 = I: s = (i == j ? 1 : 0), s = fma(-T(i,k), R(k,j), s) for k ascending, T(i,j) = s / R(j,j)
+ *   C            mult * S(i,j), S(i,j) = sum over k = max(i,j) .. r-1 ascending of fma(T(i,k), T(j,k), .), scattered through jpvt:
+ *                C = mult P [ (R11^T R11)^-1 0 ; 0 0 ] P^T, the covariance of the basic solution as MINPACK's covar defines it.  C is
+ *                stored as a full symmetric matrix, both triangles from the one computed value (bitwise symmetric); the rows and columns
+ *                of the dropped variables are exact zeros; se_j = sqrt(C_jj) of the stored value
+ *   h_i          p_i |R11^-T (P^T a_i)(0 : r)|^2: per row one forward substitution with R^T, one fma per term in ascending index order,
+ *                the squares added in ascending order; no inverse is formed.  A row with p_i == 0 gives exactly 0 and is not used
+ *                (it may hold NaN).  This costs n^2 / 2 fmas per row where going through an explicit Q costs a second factorisation's
+ *                worth of reflections; the price is an error of order kappa eps in h where Q gives n eps
+ * A result does not depend on which call or kernel computed it: the fused call below returns bitwise what the from-factor calls return
+ * on the same triangle.
+ *
+ * Section 8's conventions hold: member q lives at base + q * stride, column-major, strides count elements; the plan supplies the stream
+ * only; QR_E_ARG for bad arguments before any device is touched; batch == 0 returns 0 after the argument checks and launches nothing;
+ * inputs are never written; no scratch memory, no host wait, one launch per call.  Failure is per member and all or nothing: a non-zero
+ * info word means nothing else was written for that member; the other members are unaffected and the call returns 0.  A member's results
+ * do not depend on the batch size or on its place in the batch, and repeated calls are bitwise equal.
+ *
+ * Dependence to rounding among the columns is NOT detected by the fused call (only an exactly zero R(i,i)).  The pivoted path is
+ * qr_geqp3_batched_dev -> qr_rank_batched_dev -> qr_covar_batched_dev and qr_leverage_batched_dev with that jpvt and rank.
+ *
+ * Out of scope: several right-hand sides per member; m < n; sandwich (robust) covariance, and the covariance of 8j's robust fits beyond
+ * passing p w as the prior; leave-one-out, studentised residuals and Cook's distance (elementwise in e, h and sigma2); effective degrees
+ * of freedom of the damped fits; covariance under the constraints of 8h and 8i; a single-matrix variant; blocked or MFMA variants.
+ * ------------------------------------------------------------------------------------------- */
+#define QR_COV_UNSCALED 0     /* C = (A^T P A)^-1 */
+#define QR_COV_SCALED 1       /* C = sigma2 (A^T P A)^-1 */
+
+/* the largest m qr_gels_stats_batched_dev takes for n unknowns: the largest m <= 512 with 8 ((n + 1) ld(m) + n + 72) bytes within
+ * 160 KiB, ld(m) the smallest value >= m that is 2 mod 32 (512 for n <= 31; 256 x 63 fits); 0 if n is not taken (n < 1 or
+ * n > QR_BATCHED_MAX_N - 1).  No device is touched. */
+int qr_stats_batched_max_rows(int n);
+
+/* MINPACK covar from a triangle that exists.  dR: the upper triangle of an n x n block per member (1 <= n <= QR_BATCHED_MAX_N, ldr >= n,
+ * strideR >= ldr * n); the strict lower triangle is never read, so the in-place factors of qr_geqrf_batched_dev / qr_geqp3_batched_dev
+ * (ldr = lda, strideR = strideA) and an accumulator's R can be passed as they are.  djpvt (0-based, n per member, stridejpvt >= n),
+ * drank and dmult (one per member) may be NULL: the identity, n and 1.  dC (n x n, ldc >= n, strideC >= ldc * n) and dse (n per member,
+ * stridese >= n): either may be NULL, not both.  dinfo: 0; i + 1 for the smallest i < rank with R(i,i) == 0 exactly; -1 for a jpvt that
+ * is no permutation of 0 .. n-1, a rank outside 0 .. n or a multiplier that is negative, NaN or inf.  Rank 0 is valid: C = 0.
+ * One wave per member for n <= 32 (four members per workgroup; the rows of T in registers), one workgroup per member above (R inverted
+ * in place in LDS). */
+int qr_covar_batched_dev(qr_plan* plan, const double* dR, int n, int ldr, long long strideR,
+                         const int* djpvt, long long stridejpvt, const int* drank, const double* dmult,
+                         double* dC, int ldc, long long strideC, double* dse, long long stridese,
+                         int* dinfo, int batch);
+
+/* dH[i] = p_i |R11^-T (P^T a_i)(0 : r)|^2 for the mrows rows of dA (mrows x n, lda >= mrows, strideA >= lda * n; any mrows >= 1: the
+ * fitted rows or new points), the triangle, djpvt and drank as above.  dprior: mrows per member, strideprior apart (0: one vector shared
+ * by all members, else >= mrows; checked even when dprior is NULL), NULL: ones.  dH: mrows per member (strideH >= mrows).  dinfo: 0;
+ * i + 1 for a zero diagonal entry; -1 for a bad jpvt, a bad rank, or a prior weight that is negative, NaN or inf (in any row: no row of
+ * such a member is written).  One workgroup per member and 256 rows, one row per thread; batch * ceil(mrows / 256) must fit an int.
+ * With dprior given, every workgroup of a member reads ALL its mrows weights before it writes (that is what keeps a bad weight in any
+ * row from leaving other rows of the member written): mrows^2 / 256 reads per member.  That is nothing at a few thousand rows and
+ * about 4e9 reads at mrows = 1e6: a caller with very many rows per member feeds them in calls of some ten thousand rows each, which
+ * return the same values row by row. */
+int qr_leverage_batched_dev(qr_plan* plan, const double* dR, int n, int ldr, long long strideR,
+                            const int* djpvt, long long stridejpvt, const int* drank,
+                            const double* dA, int mrows, int lda, long long strideA,
+                            const double* dprior, long long strideprior,
+                            double* dH, long long strideH, int* dinfo, int batch);
+
+/* The fit of qr_gels_weighted_batched_dev and its statistics in ONE launch: A m x n, n <= m <= qr_stats_batched_max_rows(n), one b,
+ * prior weights as in 8j (p_i = 0 excludes a row, which may hold NaN).  cnt = the rows with p_i > 0, dof = cnt - n.  Outputs where
+ * info is 0 (every one but dX and dinfo may be NULL): dX (n; bitwise qr_gels_weighted_batched_dev's); dE (m): e = b - A x from the
+ * untouched inputs, one fma per term, exact 0 on excluded rows; dH (m): the leverages; dsigma2 = sum p_i e_i^2 / dof (+inf when
+ * dof == 0) and ddof (int); dC (n x n) and dse (n): (A^T P A)^-1 for QR_COV_UNSCALED, sigma2 times it for QR_COV_SCALED, as
+ * qr_covar_batched_dev computes them from the fit's R with dmult NULL or sigma2.  dinfo: 0; -1 a prior weight that is negative, NaN or
+ * inf; -2 cnt < n; -3 QR_COV_SCALED with dof == 0; i + 1 an exactly zero R(i,i).  Routes as in 8j: a wave per member for m <= 64 and
+ * n + 1 <= 32, else a workgroup per member with the image in LDS; R is inverted in place in the top of the image. */
+int qr_gels_stats_batched_dev(qr_plan* plan, int scaled,
+                              const double* dA, int m, int n, int lda, long long strideA,
+                              const double* dB, long long strideB,
+                              const double* dprior, long long strideprior,
+                              double* dX, long long strideX,
+                              double* dE, long long strideE,
+                              double* dH, long long strideH,
+                              double* dsigma2, int* ddof,
+                              double* dC, int ldc, long long strideC,
+                              double* dse, long long stridese,
+                              int* dinfo, int batch);
+
+/* qr_covar_batched_dev on a batched accumulator's R (section 8d), the multiplier formed on the device: sigma2 = rss[rhs] / (rows - n)
+ * (+inf when rows == n), written to dsigma2 (one per member, may be NULL); C = (R^T R)^-1 for QR_COV_UNSCALED, sigma2 times it for
+ * QR_COV_SCALED.  dinfo (acc's batch ints): 0; i + 1 for a member that holds fewer than n rows (the first zero R(i,i)); -3 for
+ * QR_COV_SCALED with rows == n; -1 for QR_COV_SCALED where sigma2 is no finite number >= 0 (a NaN or inf that was pushed sits in
+ * rss).  The state is untouched.  No host wait. */
+int qr_lsacc_batched_covar_dev(qr_lsacc_batched* acc, int scaled, int rhs,
+                               double* dC, int ldc, long long strideC, double* dse, long long stridese,
+                               double* dsigma2, int* dinfo);
+
+/* qr_gels_stats_batched_dev for a packed batch on host pointers (A: m x n, b: m, prior: m per member; prior may be NULL; all untouched):
+ * X n, E and H m, sigma2 and dof one, Cov n x n (ld n) and se n per member (all but X and info may be NULL); the outputs of a member
+ * with a non-zero info read 0.  Returns QR_E_SINGULAR if any info word is non-zero.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_stats_batched(const double* A, int m, int n, const double* b, const double* prior, int scaled, int batch,
+                           double* X, double* E, double* H, double* sigma2, int* dof, double* Cov, double* se, int* info);
+
 #ifdef __cplusplus
 }
 #endif
