@@ -220,6 +220,11 @@ _sig("qr_bvls_batched_max_rows", C.c_int, C.c_int)
 _sig("qr_bvls_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _vp, _ll, C.c_int, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp,
      _vp, C.c_int)
 _sig("qr_lstsq_bounded_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _dp, _ip, _ip)
+_sig("qr_lsei_batched_max_rows", C.c_int, C.c_int, C.c_int)
+_sig("qr_lsei_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, C.c_int,
+     C.c_double, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, C.c_int)
+_sig("qr_lstsq_inequality_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp,
+     _ip, _dp, _ip, _ip)
 _sig("qr_irls_batched_max_rows", C.c_int, C.c_int)
 _sig("qr_irls_batched_dev", C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _ll, C.c_double,
      C.c_int, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -873,6 +878,54 @@ def nnls_batched(A, b, maxit=0):
     return lstsq_bounded_batched(A, b, lo=np.zeros(A.shape[2]), hi=None, maxit=maxit)
 
 
+def lsei_batched_max_rows(n, mg):
+    """the most rows Plan.lsei_batched takes for n unknowns and mg constraint rows (qr_lsei_batched_max_rows; 0: (n, mg) is not taken at
+    all; no device)"""
+    return lib.qr_lsei_batched_max_rows(int(n), int(mg))
+
+
+def lstsq_inequality_batched(A, b, G, h, neq=0, maxit=0, rcond=0.0):
+    """min ||A_q x - b_q|| subject to G_q(0:neq) x = h_q(0:neq), G_q(neq:) x >= h_q(neq:) for every member of A (batch, m, n) and b
+    (batch, m) through qr_lstsq_inequality_batched (Lawson & Hanson's LSEI by a dual active-set loop, the loop of every member on the
+    device).  G: (mg, n) (shared by all members) or (batch, mg, n); h: (mg,) or (batch, mg); mg <= 64.  maxit: the most candidates per
+    member (<= 0: 3 mg + 1); rcond: the dependence test of a row against the set (<= 0: n eps).  Returns (X, mu, s, state, resid, iter,
+    info): X (batch, n); mu (batch, mg) with A^T (A x - b) = G^T mu, > 0 on the inequalities of the set and exactly 0 off it; s = G x - h;
+    state 1 in the set, else 0; resid[q] = ||A_q x - b_q||; iter the candidates taken; info 0, n + 1 at maxit (the last accepted pair
+    is returned, s shows what it still violates), -2 infeasible, -3 equalities exactly dependent, i + 1 an exactly zero R_a(i,i) (the
+    other outputs of such a member read 0).  A member with an info word does not raise."""
+    what = "lstsq_inequality_batched"
+    At = _packed_batch(A, what)
+    batch, n, m = At.shape
+    b = np.asarray(b, dtype=np.float64)
+    if b.ndim == 3 and b.shape[2] == 1:
+        b = b[:, :, 0]
+    if b.shape != (batch, m):
+        raise QRError(f"{what}: b must be ({batch}, {m}), one right-hand side per member, got {b.shape}", QR_E_ARG)
+    b = np.ascontiguousarray(b)
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim == 2:
+        G = np.broadcast_to(G, (batch,) + G.shape)
+    if G.ndim != 3 or G.shape[0] != batch or G.shape[2] != n:
+        raise QRError(f"{what}: G must be (mg, {n}) or ({batch}, mg, {n}), got {G.shape}", QR_E_ARG)
+    mg = G.shape[1]
+    Gt = np.ascontiguousarray(G.transpose(0, 2, 1))           # column-major members
+    h = _bound_batch(h, batch, mg, what, "h")
+    if h is None:
+        raise QRError(f"{what}: h is required", QR_E_ARG)
+    X = np.empty((batch, n))
+    mu = np.empty((batch, mg))
+    s = np.empty((batch, mg))
+    resid = np.empty(batch)
+    state = np.zeros((max(batch, 1), mg), dtype=np.intc)
+    it = np.zeros(max(batch, 1), dtype=np.intc)
+    info = np.zeros(max(batch, 1), dtype=np.intc)
+    rc = lib.qr_lstsq_inequality_batched(_p(At), m, n, _p(b), _p(Gt), mg, int(neq), _p(h), int(maxit), float(rcond), batch, _p(X), _p(mu),
+                                         _p(s), state.ctypes.data_as(_ip), _p(resid), it.ctypes.data_as(_ip), info.ctypes.data_as(_ip))
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_inequality_batched")
+    return X, mu, s, state[:batch].astype(np.int64), resid, it[:batch].astype(np.int64), info[:batch].astype(np.int64)
+
+
 QR_LOSS_LS, QR_LOSS_HUBER, QR_LOSS_BISQUARE = 0, 1, 2
 _LOSSES = {"ls": QR_LOSS_LS, "huber": QR_LOSS_HUBER, "bisquare": QR_LOSS_BISQUARE}
 
@@ -1359,6 +1412,18 @@ class Plan:
         check(lib.qr_bvls_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dB), strideB, _dptr(dlo), _dptr(dhi), stridebnd, int(maxit),
                                       _dptr(dX), strideX, _dptr(dW), strideW, _dptr(dstate), stridestate, _dptr(dresid), _dptr(diter),
                                       _dptr(dinfo), batch), "qr_bvls_batched_dev")
+
+    def lsei_batched(self, dA, m, n, lda, strideA, dB, strideB, dG, mg, neq, ldg, strideG, dH, strideH, dX, strideX, dinfo, batch, maxit=0,
+                     rcond=0.0, dMU=None, strideMU=0, dS=None, strideS=0, dstate=None, stridestate=0, dresid=None, diter=None):
+        """min ||A x - b|| subject to G(0:neq) x = h(0:neq), G(neq:mg) x >= h(neq:mg) for `batch` members in one launch: dA (m x n), dB (m
+        per member), dG (mg x n, strideG 0: shared) and dH (mg per member, strideH 0: shared) are read only; x to dX (n per member), the
+        multipliers to dMU, G x - h to dS (mg per member), the set (int32: 1 in it, else 0) to dstate, ||A x - b|| to dresid and the
+        candidate count (int32) to diter where given; maxit <= 0: 3 mg + 1; rcond <= 0: n eps; dinfo: one int32 per member (0; n + 1 at
+        maxit, the last accepted pair written; -2 infeasible, -3 dependent equalities and i + 1 for a zero R_a(i,i): nothing else is
+        written for that member)"""
+        check(lib.qr_lsei_batched_dev(self.h, _dptr(dA), m, n, lda, strideA, _dptr(dB), strideB, _dptr(dG), mg, neq, ldg, strideG, _dptr(dH),
+                                      strideH, int(maxit), float(rcond), _dptr(dX), strideX, _dptr(dMU), strideMU, _dptr(dS), strideS,
+                                      _dptr(dstate), stridestate, _dptr(dresid), _dptr(diter), _dptr(dinfo), batch), "qr_lsei_batched_dev")
 
     def irls_batched(self, loss, dA, m, n, lda, strideA, dB, strideB, dX, strideX, dinfo, batch, tune=0.0, dprior=None, strideprior=0,
                      dscale_in=None, dX0=None, strideX0=0, tol=1e-8, maxit=0, dW=None, strideW=0, dscale=None, dresid=None, diter=None,

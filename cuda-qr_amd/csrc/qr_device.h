@@ -458,6 +458,29 @@ int qrd_bv_wave_route(int m, int n);
 int qrd_bv_max_rows(int n);
 int qrd_bv_solve(void* stream, const qrd_bv_args* a);
 
+/* batched inequality-constrained least squares (qr_batched_lsei.hip, called from qr_batched_lsei.c only; mi355x_qr.h section 8l).  Per
+ * member min |A x - b| subject to G(0:neq) x = h(0:neq), G(neq:mg) x >= h(neq:mg) by a dual active-set loop inside one launch, every
+ * candidate the null-space solve of qr_batched_lse.hip on the rows of the set, refilled from the untouched inputs.
+ *   A: m x n (lda >= m), B: m per member, G: mg x n (ldg >= mg), H: mg per member, none of them written (sG == 0, sH == 0: shared); X: n
+ *   per member; MU, S (mg per member), state (mg ints per member), resid and iter (one per member) may be NULL.  1 <= n <= 63,
+ *   1 <= mg <= 64, 0 <= neq <= min(n, mg), m >= 1, m + neq >= n, maxit >= 1, rcond > 0.
+ *   info[q]: 0; n + 1 at maxit candidates (the last accepted pair is written); -2 infeasible; -3 an exactly zero R_c(i,i) at the start;
+ *   i + 1 an exactly zero R_a(i,i) (nothing but info is written for the last three).
+ * qrd_le_wave_route: m <= 64 and n + 1 <= 32, one wave per member; else one workgroup per member, m <= qrd_le_max_rows(n, mg): the
+ * largest m <= QRD_B_MAX_ROWS with 8 ((n + 1) qb_ld(m) + (n + 1) qb_ld(n) + 5 mg + 4 n + 72) bytes within 160 KiB of LDS (0: (n, mg) is
+ * not taken).  qrd_le_solve: one launch.  batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_le_args {
+    const double *A, *B, *G, *H;
+    double *X, *MU, *S, *resid;
+    int *state, *iter, *info;
+    size_t sA, sB, sG, sH, sX, sMU, sS, sstate;
+    double rcond;
+    int lda, ldg, m, n, mg, neq, maxit, batch;
+} qrd_le_args;
+int qrd_le_wave_route(int m, int n);
+int qrd_le_max_rows(int n, int mg);
+int qrd_le_solve(void* stream, const qrd_le_args* a);
+
 /* batched robust and weighted least squares (qr_batched_irls.hip, called from qr_batched_irls.c only; mi355x_qr.h section 8j).  Per member
  * iteratively reweighted least squares: the reweighting loop of every member runs inside one launch, every solve a Householder QR of the
  * rows of [A | b] (refilled from the untouched inputs) times sqrt(prior_i w_i) and one back substitution.

@@ -63,6 +63,15 @@
  * stationarity measure max over free j of |a_j^T (b - A x)| / (||a_j|| (||A|| ||x|| + ||b||)) (Frobenius norms, formed on the host), the
  * number of variables whose state is not the planted one (and of non-zero info words), the mean and the largest elimination count.
  *
+ * `./qr_device m n --batched count --lsei mg [neq]` does nothing else either: `count` seeded planted problems min ||A x - b|| subject to
+ * G(0:neq) x = h(0:neq), G(neq:mg) x >= h(neq:mg) (resident in HBM; m >= n; neq defaults to 0) go through one qr_lsei_batched_dev call.  A
+ * member is planted on the host: x* is drawn, min(floor(min(n, mg - neq) / 2), n - neq) inequality rows are active with multipliers in
+ * [0.5, 1.5] (equality rows carry +-[0.5, 1.5]), the other rows have slack in [0.5, 1.5], h = G x* - slack and b = A x* - A z with
+ * (A^T A) z = G^T mu* (Cholesky on the host): x*, mu* and the set are then the unique solution.  Printed: the time, the worst constraint
+ * violation (|G_i x - h_i| on the rows of the set, its negative part elsewhere, over |G_i| |x| + |h_i|), the worst KKT residual
+ * max_j |A^T (A x - b) - G^T mu|_j / (||a_j|| (||A|| ||x|| + ||b||) + (|G|^T |mu|)_j), the number of rows whose state is not the planted one,
+ * the mean and the largest candidate count, and the number of non-zero info words.
+ *
  * `./qr_device m n --batched count --robust frac` does nothing else either: `count` seeded planted problems b = A x* + 0.01 noise with a
  * fraction `frac` of the rows shifted by +-[0.1, 0.5] (resident in HBM) go through one qr_irls_batched_dev call with the Huber loss and its
  * defaults.  Printed: the time, the worst error ||x - x*|| / ||x*|| beside that of one qr_gels_batched_dev on copies of the same members,
@@ -1202,6 +1211,149 @@ static int batched_bvls_main(int m, int n, int count)
     return 0;
 }
 
+/* count planted problems min |A x - b| subject to G(0:neq) x = h(0:neq), G(neq:mg) x >= h(neq:mg) through one qr_lsei_batched_dev call */
+static int batched_lsei_main(int m, int n, int count, int mg, int neq)
+{
+    if (count < 1 || qr_lsei_batched_max_rows(n, mg) < 1 || neq < 0 || neq > n || neq > mg || m < n || m > qr_lsei_batched_max_rows(n, mg)) {
+        fprintf(stderr, "--batched count --lsei mg [neq] needs count >= 1, 1 <= n < %d, 1 <= mg <= 64, 0 <= neq <= min(n, mg) and "
+                        "n <= m <= qr_lsei_batched_max_rows(n, mg)\n", QR_BATCHED_MAX_N);
+        return 1;
+    }
+    int na = (n < mg - neq ? n : mg - neq) / 2;
+    if (na > n - neq) na = n - neq;
+    printf("Exact problem size: %d planted problems of %dx%d with %d constraint rows (%d equalities, %d inequalities active)\n", count, m, n, mg, neq, na);
+    const size_t nc = (size_t) count, mn = (size_t) m * n, gn = (size_t) mg * n;
+    const size_t tot = nc * (mn + (size_t) m + gn + (size_t) mg), outs = nc * ((size_t) n + 2 * (size_t) mg + 1);
+    double *Hh = malloc(sizeof(double) * tot), *O = malloc(sizeof(double) * outs), *N = malloc(sizeof(double) * (size_t) n * n);
+    double *w = malloc(sizeof(double) * (size_t) (n + m + mg)), *r = malloc(sizeof(double) * (size_t) m);
+    int *planted = malloc(sizeof(int) * nc * mg), *IO = malloc(sizeof(int) * nc * ((size_t) mg + 2));
+    if (!Hh || !O || !N || !w || !r || !planted || !IO) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    double *A = Hh, *B = A + nc * mn, *G = B + nc * m, *HH = G + nc * gn;
+    for (size_t q = 0; q < nc; q++) {
+        double *Aq = A + q * mn, *bq = B + q * m, *Gq = G + q * gn, *hq = HH + q * mg;
+        double *z = w, *xs = w + n, *mus = w + n + m;           /* (xs: n <= m entries) */
+        int* pl = planted + q * mg;
+        for (size_t i = 0; i < mn; i++) Aq[i] = (double) rand() / RAND_MAX - 0.5;
+        for (size_t i = 0; i < gn; i++) Gq[i] = (double) rand() / RAND_MAX - 0.5;
+        for (int j = 0; j < n; j++) xs[j] = 2.0 * ((double) rand() / RAND_MAX - 0.5);
+        for (int i = 0; i < mg; i++) { pl[i] = i < neq; mus[i] = 0.0; }
+        for (int c = 0; c < na; ) {                            /* na distinct inequality rows */
+            const int i = neq + rand() % (mg - neq);
+            if (!pl[i]) { pl[i] = 1; c++; }
+        }
+        for (int i = 0; i < mg; i++) {
+            const double u = 0.5 + (double) rand() / RAND_MAX;
+            if (pl[i]) mus[i] = (i < neq && (rand() & 1)) ? -u : u;
+            double s = 0.0;
+            for (int j = 0; j < n; j++) s += Gq[(size_t) j * mg + i] * xs[j];
+            hq[i] = pl[i] ? s : s - u;
+        }
+        /* (A^T A) z = G^T mu* by Cholesky; b = A (x* - z): A^T (A x* - b) = G^T mu* */
+        for (int a = 0; a < n; a++)
+            for (int c = a; c < n; c++) {
+                double s = 0.0;
+                for (int i = 0; i < m; i++) s += Aq[(size_t) a * m + i] * Aq[(size_t) c * m + i];
+                N[(size_t) c * n + a] = N[(size_t) a * n + c] = s;
+            }
+        for (int j = 0; j < n; j++) {
+            double s = 0.0;
+            for (int i = 0; i < mg; i++) s += Gq[(size_t) j * mg + i] * mus[i];
+            z[j] = s;
+        }
+        for (int j = 0; j < n; j++) {                          /* N = L L^T, L in the lower triangle (N[c * n + r], r >= c) */
+            double d = N[(size_t) j * n + j];
+            for (int k = 0; k < j; k++) d -= N[(size_t) k * n + j] * N[(size_t) k * n + j];
+            d = sqrt(d);
+            N[(size_t) j * n + j] = d;
+            for (int i = j + 1; i < n; i++) {
+                double s = N[(size_t) j * n + i];
+                for (int k = 0; k < j; k++) s -= N[(size_t) k * n + i] * N[(size_t) k * n + j];
+                N[(size_t) j * n + i] = s / d;
+            }
+        }
+        for (int i = 0; i < n; i++) {
+            double s = z[i];
+            for (int k = 0; k < i; k++) s -= N[(size_t) k * n + i] * z[k];
+            z[i] = s / N[(size_t) i * n + i];
+        }
+        for (int i = n - 1; i >= 0; i--) {
+            double s = z[i];
+            for (int k = i + 1; k < n; k++) s -= N[(size_t) i * n + k] * z[k];
+            z[i] = s / N[(size_t) i * n + i];
+        }
+        for (int i = 0; i < m; i++) {
+            double s = 0.0;
+            for (int j = 0; j < n; j++) s += Aq[(size_t) j * m + i] * (xs[j] - z[j]);
+            bq[i] = s;
+        }
+    }
+    qr_plan* plan = NULL;
+    double *dH = NULL, *dO = NULL;
+    int* dI = NULL;
+    if (qr_plan_create(&plan, m, n, 0, 0) || qr_device_malloc((void**) &dH, sizeof(double) * tot) ||
+        qr_device_malloc((void**) &dO, sizeof(double) * outs) || qr_device_malloc((void**) &dI, sizeof(int) * nc * ((size_t) mg + 2)) ||
+        qr_copy_to_device(dH, Hh, sizeof(double) * tot)) {
+        fprintf(stderr, "device setup failed\n");
+        return 1;
+    }
+    const double *dA = dH, *dB = dA + nc * mn, *dG = dB + nc * m, *dHH = dG + nc * gn;
+    double *dX = dO, *dMU = dX + nc * n, *dS = dMU + nc * mg, *dres = dS + nc * mg;
+    int *dstate = dI, *diter = dstate + nc * mg, *dinfo = diter + nc;
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {               /* (the inputs are read only: no copy between the trials) */
+        const double t0 = now();
+        int rc = qr_lsei_batched_dev(plan, dA, m, n, m, (long long) mn, dB, m, dG, mg, neq, mg, (long long) gn, dHH, mg, 0, 0.0, dX, n, dMU, mg, dS,
+                                     mg, dstate, mg, dres, diter, dinfo, count);
+        if (!rc) rc = qr_plan_sync(plan);
+        if (rc) { fprintf(stderr, "the batched call failed: %s\n", qr_strerror(rc)); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    if (qr_copy_to_host(O, dO, sizeof(double) * outs) || qr_copy_to_host(IO, dI, sizeof(int) * nc * ((size_t) mg + 2))) { fprintf(stderr, "copy back failed\n"); return 1; }
+    const double *X = O, *MU = X + nc * n;
+    const int *state = IO, *iter = state + nc * mg, *info = iter + nc;
+    int failed = 0, mismatched = 0, most = 0;
+    double worstc = 0.0, worstk = 0.0, iters = 0.0;
+    for (size_t q = 0; q < nc; q++) {
+        if (info[q]) { failed++; continue; }
+        const double *Aq = A + q * mn, *bq = B + q * m, *Gq = G + q * gn, *hq = HH + q * mg, *x = X + q * n, *mu = MU + q * mg;
+        double nA = 0.0, nx = 0.0, nb = 0.0;
+        for (size_t i = 0; i < mn; i++) nA += Aq[i] * Aq[i];
+        for (int i = 0; i < n; i++) nx += x[i] * x[i];
+        for (int i = 0; i < m; i++) nb += bq[i] * bq[i];
+        for (int i = 0; i < m; i++) {
+            double s = -bq[i];
+            for (int c = 0; c < n; c++) s += Aq[(size_t) c * m + i] * x[c];
+            r[i] = s;
+        }
+        const double nrm = sqrt(nA) * sqrt(nx) + sqrt(nb);
+        for (int i = 0; i < mg; i++) {
+            if (state[q * mg + i] != planted[q * mg + i]) mismatched++;
+            double s = -hq[i], sc = fabs(hq[i]);
+            for (int c = 0; c < n; c++) { s += Gq[(size_t) c * mg + i] * x[c]; sc += fabs(Gq[(size_t) c * mg + i] * x[c]); }
+            const double v = state[q * mg + i] ? fabs(s) : (s < 0.0 ? -s : 0.0);
+            if (sc > 0.0 && v / sc > worstc) worstc = v / sc;
+        }
+        for (int c = 0; c < n; c++) {
+            double g = 0.0, na2 = 0.0, gm = 0.0;
+            for (int i = 0; i < m; i++) { g += Aq[(size_t) c * m + i] * r[i]; na2 += Aq[(size_t) c * m + i] * Aq[(size_t) c * m + i]; }
+            for (int i = 0; i < mg; i++) { g -= Gq[(size_t) c * mg + i] * mu[i]; gm += fabs(Gq[(size_t) c * mg + i] * mu[i]); }
+            const double k1 = fabs(g) / (sqrt(na2) * nrm + gm);
+            if (k1 > worstk) worstk = k1;
+        }
+        iters += iter[q];
+        if (iter[q] > most) most = iter[q];
+    }
+    printf(" MMQR solved %d inequality-constrained %dx%d systems with %d rows of G in %f s (avg over %d)   [batch resident in HBM]\n", count, m, n, mg,
+           el / TRIALS, TRIALS);
+    printf(" worst constraint violation = %.2e   worst KKT residual = %.2e   state mismatches = %d   candidates: mean %.2f, most %d   non-zero info words = %d\n",
+           worstc, worstk, mismatched, failed < count ? iters / (count - failed) : 0.0, most, failed);
+    qr_device_free(dH); qr_device_free(dO); qr_device_free(dI);
+    qr_plan_destroy(plan);
+    free(Hh); free(O); free(N); free(w); free(r); free(planted); free(IO);
+    return 0;
+}
+
 /* count planted problems with a fraction frac of outlier rows through one qr_irls_batched_dev call (Huber), beside qr_gels_batched_dev */
 static int batched_robust_main(int m, int n, int count, double frac)
 {
@@ -1369,7 +1521,7 @@ static int batched_stats_main(int m, int n, int count)
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --robust frac | --stats]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --lsei mg [neq] | --robust frac | --stats]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -1403,6 +1555,10 @@ int main(int argc, char** argv)
                     return batched_robust_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atof(argv[k + 1]) : 0.2);
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--stats") == 0) return batched_stats_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--lsei") == 0)
+                    return batched_lsei_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atoi(argv[k + 1]) : 1,
+                                             k + 2 < argc ? atoi(argv[k + 2]) : 0);
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--bvls") == 0) return batched_bvls_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)

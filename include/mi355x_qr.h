@@ -1459,6 +1459,94 @@ int qr_lsacc_batched_covar_dev(qr_lsacc_batched* acc, int scaled, int rhs,
 int qr_lstsq_stats_batched(const double* A, int m, int n, const double* b, const double* prior, int scaled, int batch,
                            double* X, double* E, double* H, double* sigma2, int* dof, double* Cov, double* se, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8l. Batched inequality-constrained least squares (Lawson & Hanson's LSEI): for every member of a batch
+ *
+ *         min |A x - b|_2  subject to  G(0:neq, :) x = h(0:neq),  G(neq:mg, :) x >= h(neq:mg),
+ *
+ * A: m x n, G: mg x n, 0 <= neq <= min(n, mg), 1 <= mg <= 64, 1 <= n <= QR_BATCHED_MAX_N - 1, m >= 1, m + neq >= n, one b per member --
+ * what 8i leaves out: a joint limit expressed in task space, friction-cone facets, half-space collision avoidance, a monotone or convex
+ * fit, an interpolation condition together with a sign constraint.  neq == mg is 8h's problem; bounds are rows +-e_j^T of G.  The
+ * active-set loop of every member runs on the device: one launch whatever the batch size; nothing waits on the host.
+ *
+ * The method is a dual active-set loop whose every candidate is 8h's null-space solve (the textbook reduction LSI -> LDP -> NNLS is not
+ * used: it loses the constraints to kappa eps on graded columns).  Per member the state is the working set W (rows < neq are in it for
+ * good), mu (mg entries), x, a ban set and the count it.  A candidate of a row set S is the solution of min |A x - b| subject to
+ * G_S x = h_S by steps 1 to 8 of 8h (a plain factorisation and solve of A when S is empty): x_S and zeta = -lambda_S, so that
+ * A^T (A x_S - b) = G_S^T zeta.  The rows of S are taken in ascending index order, a pending row t last.
+ *   1. Start.  W = {0 .. neq-1}; it = 1; (x, mu_W) = candidate(W).  An exactly zero R_c(i,i) gives info -3; an exactly zero R_a(i,i),
+ *      here or in any later candidate, gives info i + 1; in both cases nothing else is written.
+ *   2. Outer test.  s = G x - h from the untouched G.  Among the rows i >= neq outside W and not banned the most negative s_i, ties to
+ *      the smallest index.  None < 0: done, info 0.  Otherwise t is that row, mu_t = 0, pend = true.
+ *   3. Count.  it == maxit: done, info n + 1, the last accepted (x, mu) is written.  Otherwise ++it.
+ *   4. Dependence.  [G_W^T | G_t^T] is factored over its first |W| columns, the last riding along; rho is the norm of that column's rows
+ *      |W| .. n-1.  If |W| == n or rho <= rcond |G_t|_2: c = R_c^-1 (its top |W| entries); over the i in W with i >= neq and c_i > 0,
+ *      theta = min mu_i / c_i, ties to the smallest index k.  No such i: info -2 (infeasible), nothing else written.  Otherwise
+ *      mu_W -= theta c, mu_t += theta, mu_k = 0 exactly and k leaves W, every other inequality member with mu <= 0 is set to 0 and
+ *      leaves; pend = false; go to 3.  Otherwise the same factorisation is completed with t's column: nothing is factored twice.
+ *   5. Candidate.  (x_c, zeta) = candidate(W + {t}).
+ *   6. Anti-cycling, only when pend is set, which it clears: zeta_t <= 0: t is banned, mu_t = 0, go to 2.
+ *   7. Accept.  zeta_i > 0 for every inequality i in W + {t}: W gains t, mu = zeta on W and 0 elsewhere, x = x_c, the bans are
+ *      lifted, go to 2.
+ *   8. Blocked step.  Over the inequality i in W + {t} with zeta_i <= 0, alpha = min mu_i / (mu_i - zeta_i), ties to the smallest index
+ *      k.  k == t (this does not happen in exact arithmetic): nothing moves -- W and mu are those of the last accepted pair again --, t
+ *      is banned, go to 2.  Otherwise mu_i += alpha (zeta_i - mu_i) over W + {t}, equalities included; mu_k = 0 exactly and k leaves
+ *      W; every other inequality member with mu <= 0 is set to 0 and leaves.  Go to 3 (t stays pending, pend stays false).
+ * Every candidate is factored from scratch from the untouched inputs.  it counts every candidate and every dependence step, and
+ * it <= maxit is the only loop bound; maxit <= 0 means 3 mg + 1.  rcond <= 0 means n eps, the size a dependent column's diagonal is left
+ * at by a Householder factorisation of n rows.  A comparison with a NaN is false and leads towards the count.
+ *
+ * Section 8's conventions hold: member q lives at base + q * stride, column-major, strides count elements; the plan supplies the stream
+ * only; batch == 0 returns 0 after the argument checks and launches nothing.  The inputs are never written.  strideG == 0 shares one G,
+ * strideH == 0 one h, across the batch.
+ *
+ * Outputs: x of the last accepted candidate; mu of that candidate (zeta on its set: > 0 on the inequalities of the set, either sign on
+ * the equalities, exactly 0 elsewhere); state (1 in the set, else 0); s = G x - h and resid = |A x - b| recomputed from the untouched
+ * A, G and the returned x; iter, the count.
+ *
+ * dinfo[q]: 0 solved; n + 1 the count was reached: the last accepted pair IS written, with s showing what it still violates; -2
+ * infeasible; -3 equalities exactly dependent; i + 1 an exactly zero R_a(i,i): nothing but info is written for the last three.  The
+ * other members are unaffected and the call returns 0.  Dependence to rounding among the columns of A on a null space is NOT detected,
+ * as in 8h.
+ *
+ * Routes, chosen from the shape alone.  m <= 64 and n + 1 <= 32: one wave per member, four members per workgroup.  Otherwise one
+ * workgroup per member with the image of A and the factors of G_S^T in LDS, for m <= qr_lsei_batched_max_rows(n, mg): the largest
+ * m <= 512 with 8 ((n + 1) ld(m) + (n + 1) ld(n) + 5 mg + 4 n + 72) bytes within 160 KiB, ld(r) the smallest value >= r that is 2 mod
+ * 32.  A member's results do not depend on the batch size or on its place in the batch, and repeated calls are bitwise equal.  With
+ * neq == mg x is bitwise qr_gglse_batched_dev's; where no row is ever violated x is bitwise qr_gels_batched_dev's.
+ *
+ * Out of scope: several right-hand sides per member; mg > 64; a warm start from a given set; updating factors across set changes; a
+ * single-matrix variant; blocked or MFMA variants.
+ * ------------------------------------------------------------------------------------------- */
+
+/* the largest m taken for n unknowns and mg constraint rows (at most 512); 0 if (n, mg) is not taken (n < 1, n > QR_BATCHED_MAX_N - 1,
+ * mg < 1 or mg > 64).  No device is touched. */
+int qr_lsei_batched_max_rows(int n, int mg);
+
+/* dA: m x n (lda >= m, strideA >= lda * n); dB: m per member (strideB >= m); dG: mg x n (ldg >= mg; strideG 0: one G shared by all
+ * members, else >= ldg * n); dH: mg per member (strideH 0: shared, else >= mg); dX: n per member (strideX >= n); dMU, dS (may be NULL):
+ * mg per member (strideMU, strideS >= mg); dstate (may be NULL): mg ints per member (stridestate >= mg); dresid, diter (may be NULL) and
+ * dinfo: one per member.  QR_E_ARG, before any device is touched, for a shape or an operand outside these rules. */
+int qr_lsei_batched_dev(qr_plan* plan,
+                        const double* dA, int m, int n, int lda, long long strideA,
+                        const double* dB, long long strideB,
+                        const double* dG, int mg, int neq, int ldg, long long strideG,
+                        const double* dH, long long strideH,
+                        int maxit, double rcond,
+                        double* dX, long long strideX,
+                        double* dMU, long long strideMU,
+                        double* dS, long long strideS,
+                        int* dstate, long long stridestate,
+                        double* dresid, int* diter,
+                        int* dinfo, int batch);
+
+/* The same for a packed batch on host pointers (A: m x n, b: m, G: mg x n, h: mg per member, all untouched): X n, MU, S and state mg
+ * per member, resid, iter and info one per member (MU, S, state, resid and iter may be NULL); the outputs of a member with info -2, -3
+ * or i + 1 read 0.  Returns QR_E_SINGULAR if any info word is non-zero.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_inequality_batched(const double* A, int m, int n, const double* b, const double* G, int mg, int neq, const double* h,
+                                int maxit, double rcond, int batch,
+                                double* X, double* MU, double* S, int* state, double* resid, int* iter, int* info);
+
 #ifdef __cplusplus
 }
 #endif
