@@ -38,6 +38,22 @@ int qrd_gemm_tn_update_even(void* stream, int M, int N, int K, double alpha, con
                             int ldb, double beta, double* C, int ldc, double* slabs, size_t slab_cap, int nwg);
 long long qrd_tn_even_launches(void);       /* even-split launches so far in this process */
 int qrd_tn_even_last_grid(void);            /* workgroups of the last one */
+/* Kernel tests only: the route the last call of qrd_gemm_nn, qrd_gemm_nn_update / _update2, qrd_gemm_tn / _tn_update (/ _wide / _even),
+ * qrd_gemm_nn_batch or qrd_slab_reduce took, written by the launch functions where they decide (one record for the process; a call that
+ * returns before it launches anything leaves the record cleared but for the entry and the serial).  Returns the serial.
+ *   out[0] entry: 1 nn, 2 nn_update, 3 tn, 4 nn_batch, 5 slab_reduce          out[1] tile TI TJ as two digits (44, 41, 22, 11, 14)
+ *   out[2], out[3] the fast interior Mi, Ni (0, 0: one guarded launch over everything; MIXED: the whole M, N)
+ *   out[4] ksplit (slabs summed, for slab_reduce; workgroups, for the even split)      out[5] row piece of the reduction (0: none ran)
+ *   out[6] flag bits (QRD_ROUTE_*)                                            out[7] serial number of the record */
+#define QRD_ROUTE_FAST 1        /* a FAST (unguarded) instantiation ran on the interior */
+#define QRD_ROUTE_MIXED 2       /* gemm_tn_kernel<.., MIXED>: one launch, edge tiles guarded */
+#define QRD_ROUTE_WIDE 4        /* gemm_tn_wide_kernel */
+#define QRD_ROUTE_EVEN 8        /* the even static K split */
+#define QRD_ROUTE_KREM 16       /* K % 16 remainder split: the record is the whole-k-tile part's */
+#define QRD_ROUTE_TM 32         /* Tm folded in by the reduction */
+#define QRD_ROUTE_DIRECT 64     /* no slabs: the product kernel wrote C itself */
+#define QRD_ROUTE_W8 128        /* gemm_nn_w8_kernel on the interior */
+int qrd_gemm_last_route(int out[8]);
 /* second-generation wide update (qr_gemm_nt.hip): W kept transposed, direct-to-LDS tile loads */
 int qrd_gemm2_init(void);
 int qrd_gemm_nt_ok(int M, int N, int K, const double* A, int lda, const double* Bt, int ldbt, const double* C, int ldc);

@@ -725,6 +725,37 @@ __global__ void stream_copy_kernel(const v2d* __restrict__ src, v2d* __restrict_
 // ================================================================================================
 static inline int vec_ok(const void* p, int ld) { return (((uintptr_t) p) % 16 == 0) && (ld % 2 == 0); }
 
+// The route of the last product call (qrd_gemm_last_route, kernel tests only): one record for the process, relaxed stores by the launch
+// functions below at the point where they decide, so that a test can assert the branch a case was written for without a second copy of the
+// rules.  route_begin (the extern "C" entries) clears the record and names the entry; t_route_quiet silences the nested second half of the
+// K % 16 remainder split on its own host thread.
+enum { ROUTE_ENTRY, ROUTE_TILE, ROUTE_MI, ROUTE_NI, ROUTE_KSPLIT, ROUTE_PIECE, ROUTE_FLAGS, ROUTE_SERIAL };
+enum { ENTRY_NN = 1, ENTRY_NN_UPDATE, ENTRY_TN, ENTRY_NN_BATCH, ENTRY_SLAB_REDUCE };
+static std::atomic<int> g_route[8];
+static thread_local bool t_route_quiet = false;
+static inline void route_set(int field, int v)
+{
+    if (!t_route_quiet) g_route[field].store(v, std::memory_order_relaxed);
+}
+static inline void route_flag(int bits)
+{
+    if (!t_route_quiet) g_route[ROUTE_FLAGS].fetch_or(bits, std::memory_order_relaxed);
+}
+static inline void route_begin(int entry)
+{
+    if (t_route_quiet) return;
+    for (int f = ROUTE_TILE; f <= ROUTE_FLAGS; ++f) g_route[f].store(0, std::memory_order_relaxed);
+    g_route[ROUTE_ENTRY].store(entry, std::memory_order_relaxed);
+    g_route[ROUTE_SERIAL].fetch_add(1, std::memory_order_relaxed);
+}
+static inline void route_tiles(int tile, int Mi, int Ni, int flags)
+{
+    route_set(ROUTE_TILE, tile);
+    route_set(ROUTE_MI, Mi);
+    route_set(ROUTE_NI, Ni);
+    route_flag(flags);
+}
+
 // Launch helpers.  The FAST instantiation runs on the largest tile-aligned interior of the problem; the
 // ragged right / bottom strips (and everything, when operands are not 16-byte aligned or K % 16 != 0)
 // go to the guarded instantiation as separate launches.
@@ -748,12 +779,14 @@ static int launch_nn(hipStream_t s, int M, int N, int K, double alpha, const dou
     constexpr int BM = 32 * TI, BN = 32 * TJ;
     const bool al = vec_ok(A, lda) && vec_ok(B, ldb) && (K % BK) == 0;
     const int Mi = al ? (M / BM) * BM : 0, Ni = al ? (N / BN) * BN : 0;
+    route_tiles(10 * TI + TJ, 0, 0, 0);
     if (!(Mi > 0 && Ni > 0)) return launch_nn1<TI, TJ, false>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
     // small ragged products sit on the panel's critical path, where a second (edge) launch costs more than guarded loads
     // (round 6 re-measured the 0.4 GFLOP threshold: at 0.06 GFLOP 2000^2 loses 8 %, 4096^2 at nb 64 3 %; and an edge-tiles-inside-the-fast-grid
     // form like gemm_tn_kernel<.., MIXED> spills here -- 158 VGPRs -- and loses to both.  profiles/NOTES.md)
     if ((Mi < M || Ni < N) && (double) M * N * K < 4e8)
         return launch_nn1<TI, TJ, false>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
+    route_tiles(10 * TI + TJ, Mi, Ni, QRD_ROUTE_FAST);
     int rc = launch_nn1<TI, TJ, true, TAG>(s, Mi, Ni, K, alpha, A, lda, B, ldb, beta, C, ldc);
     if (!rc && Ni < N)      /* right strip: all rows, columns [Ni, N) */
         rc = launch_nn1<TI, TJ, false>(s, M, N - Ni, K, alpha, A, lda, B + (size_t) Ni * ldb, ldb, beta,
@@ -812,17 +845,20 @@ static int launch_tn(hipStream_t s, int M, int N, int K, int ksplit, int kchunk,
     constexpr int BM = 32 * TI, BN = 32 * TJ;
     const bool al = vec_ok(A, lda) && vec_ok(B, ldb) && (K % BK) == 0;
     const int Mi = al ? (M / BM) * BM : 0, Ni = al ? (N / BN) * BN : 0;
+    route_tiles(10 * TI + TJ, 0, 0, 0);
     if (!(Mi > 0 && Ni > 0))
         return launch_tn1<TI, TJ, false>(s, M, N, K, ksplit, kchunk, alpha, A, lda, B, ldb, beta, C, ldc, slab_stride);
     if constexpr (TI == 4 && TJ == 4 && TAG <= 1) {
         if (Mi < M || Ni < N) {         // ragged: one launch over all tiles, the edge tiles guarded (gemm_tn_kernel<.., MIXED>)
             const size_t shm = sizeof(double) * (2 * BM * LDKF + 2 * BN * LDKF);
             dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN, ksplit);
+            route_tiles(10 * TI + TJ, M, N, QRD_ROUTE_FAST | QRD_ROUTE_MIXED);
             hipLaunchKernelGGL((gemm_tn_kernel<TI, TJ, true, TAG, true>), grid, dim3(256), shm, s, M, N, K, kchunk, alpha, A, lda, B, ldb,
                                beta, C, ldc, slab_stride);
             return (int) hipGetLastError();
         }
     }
+    route_tiles(10 * TI + TJ, Mi, Ni, QRD_ROUTE_FAST);
     int rc = launch_tn1<TI, TJ, true, TAG>(s, Mi, Ni, K, ksplit, kchunk, alpha, A, lda, B, ldb, beta, C, ldc, slab_stride);
     if (!rc && Ni < N)
         rc = launch_tn1<TI, TJ, false>(s, M, N - Ni, K, ksplit, kchunk, alpha, A, lda, B + (size_t) Ni * ldb, ldb, beta,
@@ -991,6 +1027,7 @@ int qrd_gemm_nn_update2(void* stream, int M, int N, int K, double alpha, const d
 static int gemm_nn_update_impl(void* stream, int M, int N, int K, double alpha, const double* A, int lda, const double* B,
                                int ldb, double beta, double* C, int ldc, int tag)
 {
+    route_begin(ENTRY_NN_UPDATE);
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     hipStream_t s = (hipStream_t) stream;
     const bool al = vec_ok(A, lda) && vec_ok(B, ldb) && (K % BK) == 0;
@@ -998,6 +1035,7 @@ static int gemm_nn_update_impl(void* stream, int M, int N, int K, double alpha, 
     if (nn_waves() != 8 || beta != 1.0 || (alpha != 1.0 && alpha != -1.0) || !al || Mi == 0 || Ni == 0)
         return launch_nn<4, 4, 1>(s, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
     const size_t shm = sizeof(double) * (2 * BK * (128 + 16) + 2 * 128 * LDKF);
+    route_tiles(44, Mi, Ni, QRD_ROUTE_FAST | QRD_ROUTE_W8);
     if (tag == 0)
         hipLaunchKernelGGL(gemm_nn_w8_kernel<0>, dim3(Mi / 128, Ni / 128), dim3(512), shm, s, Mi, Ni, K, alpha, A, lda, B, ldb, C, ldc);
     else
@@ -1030,6 +1068,7 @@ int qrd_gemm_nn(void* stream, int M, int N, int K, double alpha, const double* A
                 int ldb, double beta, double* C, int ldc)
 {
     hipStream_t s = (hipStream_t) stream;
+    route_begin(ENTRY_NN);
     if (M <= 0 || N <= 0) return 0;
     if (K <= 0) {   // C = beta*C
         if (beta == 1.0) return 0;
@@ -1152,6 +1191,9 @@ int qrd_gemm_tn_dual(void* stream, int N1, int N2, int K, const double* A, int l
 // out (M x N, ldo) = sum of nslab slabs (slab z at slabs + z*stride, ld lds), fixed order
 int qrd_slab_reduce(void* stream, int M, int N, int nslab, const double* slabs, int lds, size_t stride, double* out, int ldo)
 {
+    route_begin(ENTRY_SLAB_REDUCE);
+    route_set(ROUTE_KSPLIT, nslab);
+    route_set(ROUTE_PIECE, 256);
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(N, (M + 255) / 256), dim3(256), 0, (hipStream_t) stream, M, N, nslab, slabs, lds, stride,
                        (const double*) nullptr, 0, 0.0, out, ldo, 256, N, (double*) nullptr, 0);
     return (int) hipGetLastError();
@@ -1183,6 +1225,11 @@ static std::atomic<long long> g_tn_even_launches{0};
 static std::atomic<int> g_tn_even_last_grid{0};
 long long qrd_tn_even_launches(void) { return g_tn_even_launches.load(); }
 int qrd_tn_even_last_grid(void) { return g_tn_even_last_grid.load(); }
+int qrd_gemm_last_route(int out[8])
+{
+    for (int f = 0; f < 8; ++f) out[f] = g_route[f].load(std::memory_order_relaxed);
+    return out[ROUTE_SERIAL];
+}
 
 // Modelled cost, in K rows of one workgroup slot like the split-K rule's, of the even split on G workgroups: every workgroup walks
 // ceil(U / G) k-tiles; it pays the fixed cost of a launch's workgroup once and a partial-tile store plus an operand prologue for
@@ -1200,6 +1247,7 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
                         int ldt, int tag, int even)
 {
     hipStream_t s = (hipStream_t) stream;
+    if (even != -2) route_begin(ENTRY_TN);       // (-2: the first half of the remainder split below, inside its caller's record)
     if (M <= 0 || N <= 0) return 0;
     if (Tm && M > 256) return -2;
     // K not a multiple of the k-tile (matrix heights that are not multiples of 16): the fast kernels cannot take it, and a guarded K loop over
@@ -1208,10 +1256,14 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
     // the wide product 32.7 -> 45.7 TFLOP/s; from 4 GFLOP on -- 8200 x 2056 at nb 128, 2 GFLOP per product, loses 3 % to the extra launch)
     if (K % BK != 0 && K >= 16 * BK && Tm == nullptr && vec_ok(A, lda) && vec_ok(B, ldb) && (double) M * N * K >= 4e9) {
         const int Kf = K - K % BK;
+        route_flag(QRD_ROUTE_KREM);
         // (even = -2: the remainder split keeps the split-K rule for its whole k-tiles, whatever the caller or the model would choose)
         const int rc0 = gemm_tn_impl(stream, M, N, Kf, alpha, A, lda, B, ldb, beta, C, ldc, slabs, slab_cap, nullptr, 0, tag, -2);
         if (rc0) return rc0;
-        return gemm_tn_impl(stream, M, N, K - Kf, alpha, A + Kf, lda, B + Kf, ldb, 1.0, C, ldc, nullptr, 0, nullptr, 0, 0);
+        t_route_quiet = true;
+        const int rc1 = gemm_tn_impl(stream, M, N, K - Kf, alpha, A + Kf, lda, B + Kf, ldb, 1.0, C, ldc, nullptr, 0, nullptr, 0, 0);
+        t_route_quiet = false;
+        return rc1;
     }
     int ti, tj;
     const bool shortk = (K <= 512 && Tm == nullptr);     // e.g. W = T^T Y: one K slice, small tiles for parallelism
@@ -1277,6 +1329,8 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
             hipLaunchKernelGGL(tile_reduce_kernel, dim3(etiles, 8), dim3(256), 0, s, M / 128, etiles, nkt, G, slabs, C, ldc);
             g_tn_even_launches.fetch_add(1);
             g_tn_even_last_grid.store(G);
+            route_tiles(44, M, N, QRD_ROUTE_FAST | QRD_ROUTE_EVEN);
+            route_set(ROUTE_KSPLIT, G);
             return (int) hipGetLastError();
         }
     }
@@ -1288,6 +1342,8 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
     const int ldd = direct ? ldc : M;
     const double b2 = direct ? beta : 0.0;
     if (!direct && (slabs == nullptr || slab_cap < per)) return -3;
+    route_set(ROUTE_KSPLIT, ksplit);
+    route_flag((direct ? QRD_ROUTE_DIRECT : 0) | (Tm ? QRD_ROUTE_TM : 0));
     int rc;
     if (ti == 1 && tj == 4) rc = launch_tn<1, 4>(s, M, N, K, ksplit, kchunk, alpha, A, lda, B, ldb, b2, dst, ldd, per);
     else if (ti == 1) rc = launch_tn<1, 1>(s, M, N, K, ksplit, kchunk, alpha, A, lda, B, ldb, b2, dst, ldd, per);
@@ -1295,6 +1351,7 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
     else if (wide) {
         // interior rows (multiples of 128) on the wide kernel, the ragged rest on the guarded 128 x 128 kernel, same K slices
         const int Mi = (M / 128) * 128;
+        route_tiles(44, Mi, N, QRD_ROUTE_FAST | QRD_ROUTE_WIDE);
         hipLaunchKernelGGL(gemm_tn_wide_kernel<1>, dim3(Mi / 128, N / 256, ksplit), dim3(512), sizeof(double) * (2 * (128 + 256) * LDKF), s,
                            K, kchunk, A, lda, B, ldb, dst, ldd, per);
         rc = (int) hipGetLastError();
@@ -1310,6 +1367,7 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
         // many slabs (tall-skinny products): shorter row pieces per workgroup, so that more threads share the slab index
         int piece = 256;
         if (Tm == nullptr && ksplit >= 32 && M >= 64) piece = ksplit >= 128 ? 32 : 64;
+        route_set(ROUTE_PIECE, piece);
         hipLaunchKernelGGL(slab_reduce_kernel, dim3(N, (M + piece - 1) / piece), dim3(256), 0, s, M, N, ksplit, slabs, M, per, Tm, ldt,
                            beta, C, ldc, piece, N, (double*) nullptr, 0);
         rc = (int) hipGetLastError();
@@ -1320,11 +1378,13 @@ static int gemm_tn_impl(void* stream, int M, int N, int K, double alpha, const d
 int qrd_gemm_nn_batch(void* stream, int M, int N, int K, double alpha, const double* A, int lda, size_t sA,
                       const double* B, int ldb, size_t sB, double beta, double* C, int ldc, size_t sC, int batch)
 {
+    route_begin(ENTRY_NN_BATCH);
     if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return 0;
     const size_t shm = sizeof(double) * (2 * BK * (32 + 16) + 2 * 32 * LDKF);
     dim3 grid((M + 31) / 32, (N + 31) / 32, batch);
     const bool fast = vec_ok(A, lda) && vec_ok(B, ldb) && (sA % 2) == 0 && (sB % 2) == 0 && (K % BK) == 0 && (M % 32) == 0 &&
                       (N % 32) == 0;
+    route_tiles(11, fast ? M : 0, fast ? N : 0, fast ? QRD_ROUTE_FAST : 0);
     if (fast)
         hipLaunchKernelGGL((gemm_nn_batch_kernel<1, 1, true>), grid, dim3(256), shm, (hipStream_t) stream, M, N, K, alpha, A,
                            lda, sA, B, ldb, sB, beta, C, ldc, sC);
