@@ -24,6 +24,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 #define CHECK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
@@ -79,34 +80,32 @@ int qr_gels_batched_dev(qr_plan* p, double* dA, int m, int n, int lda, long long
     return qrd_b_trsm(p->stream, dA, n, lda, sa, dB, nrhs, ldb, sb, dinfo, batch);
 }
 
-/* the host-pointer twins: a plan of their own, one device allocation, packed batches */
+/* R (n x n, packed) of every member from the factored images F (m x n, packed) */
+static void upper_triangles(const double* F, int m, int n, size_t nb, double* R)
+{
+    for (size_t q = 0; q < nb; ++q)
+        for (int c = 0; c < n; ++c)
+            for (int r = 0; r < n; ++r) R[q * n * n + (size_t) c * n + r] = r <= c ? F[q * (size_t) m * n + (size_t) c * m + r] : 0.0;
+}
+
+/* the host-pointer twins, here and in sections 8b and 8c: packed batches, staged as qr_stage.h describes */
 int qr_thin_batched(const double* A, int m, int n, int batch, double* Q, double* R)
 {
     if (!A || !Q || !R || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || batch < 0) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t mn = (size_t) m * n, nb = (size_t) batch;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, m, n, 0, 0));
-    double* d = NULL;
-    double *dA = NULL, *dQ = NULL, *dtau = NULL;
-    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (2 * mn + (size_t) n));
-    if (!rc) { dA = d; dQ = d + nb * mn; dtau = dQ + nb * mn; }
     double* F = (double*) malloc(sizeof(double) * nb * mn);
-    if (!rc && !F) rc = QR_E_ALLOC;
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qr_geqrf_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, batch);
-    if (!rc) rc = qr_orgqr_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dQ, m, (long long) mn, batch);
-    if (!rc) rc = qrd_d2h(p->stream, Q, dQ, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_d2h(p->stream, F, dA, sizeof(double) * nb * mn);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            for (int c = 0; c < n; ++c)
-                for (int r = 0; r < n; ++r) R[q * n * n + (size_t) c * n + r] = r <= c ? F[q * mn + (size_t) c * m + r] : 0.0;
+    if (!F) return QR_E_ALLOC;
+    double *dA, *dQ, *dtau;
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, F, 0), QR_STAGE_F64(dQ, nb * mn, NULL, Q, 0), QR_STAGE_F64(dtau, nb * (size_t) n, NULL, NULL, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m, n, t, QR_STAGE_COUNT(t));
+    if (!rc) rc = qr_geqrf_batched_dev(st.plan, dA, m, n, m, (long long) mn, dtau, n, batch);
+    if (!rc) rc = qr_orgqr_batched_dev(st.plan, dA, m, n, m, (long long) mn, dtau, n, dQ, m, (long long) mn, batch);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc) upper_triangles(F, m, n, nb, R);
+    qr_stage_close(&st);
     free(F);
-    if (d) qrd_free(d);
-    qr_plan_destroy(p);
     return rc;
 }
 
@@ -115,23 +114,16 @@ int qr_lstsq_batched(const double* A, int m, int n, const double* B, int nrhs, i
     if (!A || !B || !X || !info || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || nrhs < 1 || batch < 0) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t mn = (size_t) m * n, mr = (size_t) m * nrhs, nb = (size_t) batch;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, m, n, 0, 0));
-    double* d = NULL;
-    int* dinfo = NULL;
-    double *dA = NULL, *dB = NULL, *dtau = NULL;
-    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (mn + mr + (size_t) n));
-    if (!rc) { dA = d; dB = d + nb * mn; dtau = dB + nb * mr; }
-    if (!rc) rc = qrd_malloc((void**) &dinfo, sizeof(int) * nb);
     double* C = (double*) malloc(sizeof(double) * nb * mr);
-    if (!rc && !C) rc = QR_E_ALLOC;
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(p->stream, dB, B, sizeof(double) * nb * mr);
-    if (!rc) rc = qr_gels_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dB, nrhs, m, (long long) mr, dinfo, batch);
-    if (!rc) rc = qrd_d2h(p->stream, C, dB, sizeof(double) * nb * mr);
-    if (!rc) rc = qrd_d2h(p->stream, info, dinfo, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
+    if (!C) return QR_E_ALLOC;
+    double *dA, *dB, *dtau;
+    int* dinfo;
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dB, nb * mr, B, C, 0), QR_STAGE_F64(dtau, nb * (size_t) n, NULL, NULL, 0),
+                         QR_STAGE_I32(dinfo, nb, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m, n, t, QR_STAGE_COUNT(t));
+    if (!rc) rc = qr_gels_batched_dev(st.plan, dA, m, n, m, (long long) mn, dtau, n, dB, nrhs, m, (long long) mr, dinfo, batch);
+    rc = qr_stage_fetch(&st, rc);
     if (!rc)
         for (size_t q = 0; q < nb; ++q) {
             for (int j = 0; j < nrhs; ++j) {
@@ -145,10 +137,8 @@ int qr_lstsq_batched(const double* A, int m, int n, const double* B, int nrhs, i
             }
             if (info[q]) rc = QR_E_SINGULAR;
         }
+    qr_stage_close(&st);
     free(C);
-    if (dinfo) qrd_free(dinfo);
-    if (d) qrd_free(d);
-    qr_plan_destroy(p);
     return rc;
 }
 
@@ -208,32 +198,20 @@ int qr_thin_pivoted_batched(const double* A, int m, int n, int batch, double* Q,
     if (!A || !Q || !R || !jpvt || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || batch < 0) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t mn = (size_t) m * n, nb = (size_t) batch;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, m, n, 0, 0));
-    double* d = NULL;
-    int* dj = NULL;
-    double *dA = NULL, *dQ = NULL, *dtau = NULL;
-    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (2 * mn + (size_t) n));
-    if (!rc) { dA = d; dQ = d + nb * mn; dtau = dQ + nb * mn; }
-    if (!rc) rc = qrd_malloc((void**) &dj, sizeof(int) * nb * (size_t) n);
     double* F = (double*) malloc(sizeof(double) * nb * mn);
-    if (!rc && !F) rc = QR_E_ALLOC;
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qr_geqp3_batched_dev(p, dA, m, n, m, (long long) mn, dj, n, dtau, n, batch);
-    if (!rc) rc = qr_orgqr_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dQ, m, (long long) mn, batch);
-    if (!rc) rc = qrd_d2h(p->stream, Q, dQ, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_d2h(p->stream, F, dA, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_d2h(p->stream, jpvt, dj, sizeof(int) * nb * (size_t) n);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            for (int c = 0; c < n; ++c)
-                for (int r = 0; r < n; ++r) R[q * n * n + (size_t) c * n + r] = r <= c ? F[q * mn + (size_t) c * m + r] : 0.0;
+    if (!F) return QR_E_ALLOC;
+    double *dA, *dQ, *dtau;
+    int* dj;
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, F, 0), QR_STAGE_F64(dQ, nb * mn, NULL, Q, 0), QR_STAGE_F64(dtau, nb * (size_t) n, NULL, NULL, 0),
+                         QR_STAGE_I32(dj, nb * (size_t) n, NULL, jpvt, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m, n, t, QR_STAGE_COUNT(t));
+    if (!rc) rc = qr_geqp3_batched_dev(st.plan, dA, m, n, m, (long long) mn, dj, n, dtau, n, batch);
+    if (!rc) rc = qr_orgqr_batched_dev(st.plan, dA, m, n, m, (long long) mn, dtau, n, dQ, m, (long long) mn, batch);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc) upper_triangles(F, m, n, nb, R);
+    qr_stage_close(&st);
     free(F);
-    if (dj) qrd_free(dj);
-    if (d) qrd_free(d);
-    qr_plan_destroy(p);
     return rc;
 }
 
@@ -244,35 +222,23 @@ int qr_lstsq_pivoted_batched(const double* A, int m, int n, const double* B, int
         return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t mn = (size_t) m * n, mr = (size_t) m * nrhs, nb = (size_t) batch;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, m, n, 0, 0));
-    double* d = NULL;
-    int* di = NULL;
-    int *dj = NULL, *drank = NULL;
-    double *dA = NULL, *dB = NULL, *dtau = NULL, *dres = NULL;
-    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (mn + mr + (size_t) n + (size_t) nrhs));
-    if (!rc) { dA = d; dB = d + nb * mn; dtau = dB + nb * mr; dres = dtau + nb * (size_t) n; }
-    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * ((size_t) n + 1));
-    if (!rc) { dj = di; drank = di + nb * (size_t) n; }
     double* C = (double*) malloc(sizeof(double) * nb * mr);
-    if (!rc && !C) rc = QR_E_ALLOC;
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(p->stream, dB, B, sizeof(double) * nb * mr);
+    if (!C) return QR_E_ALLOC;
+    double *dA, *dB, *dtau, *dres;
+    int *dj, *drank;
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dB, nb * mr, B, C, 0), QR_STAGE_F64(dtau, nb * (size_t) n, NULL, NULL, 0),
+                         QR_STAGE_F64(dres, nb * (size_t) nrhs, NULL, resid, 0), QR_STAGE_I32(dj, nb * (size_t) n, NULL, jpvt, 0),
+                         QR_STAGE_I32(drank, nb, NULL, rank, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m, n, t, QR_STAGE_COUNT(t));
     if (!rc)
-        rc = gelsx_batched(p, dA, m, n, m, (long long) mn, dj, n, dtau, n, dB, nrhs, m, (long long) mr, rcond, dres, drank, batch, minnorm != 0);
-    if (!rc) rc = qrd_d2h(p->stream, C, dB, sizeof(double) * nb * mr);
-    if (!rc && resid) rc = qrd_d2h(p->stream, resid, dres, sizeof(double) * nb * (size_t) nrhs);
-    if (!rc && rank) rc = qrd_d2h(p->stream, rank, drank, sizeof(int) * nb);
-    if (!rc && jpvt) rc = qrd_d2h(p->stream, jpvt, dj, sizeof(int) * nb * (size_t) n);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
+        rc = gelsx_batched(st.plan, dA, m, n, m, (long long) mn, dj, n, dtau, n, dB, nrhs, m, (long long) mr, rcond, dres, drank, batch, minnorm != 0);
+    rc = qr_stage_fetch(&st, rc);
     if (!rc)
         for (size_t q = 0; q < nb; ++q)
             for (int j = 0; j < nrhs; ++j) memcpy(X + (q * nrhs + j) * n, C + q * mr + (size_t) j * m, sizeof(double) * (size_t) n);
+    qr_stage_close(&st);
     free(C);
-    if (di) qrd_free(di);
-    if (d) qrd_free(d);
-    qr_plan_destroy(p);
     return rc;
 }
 
@@ -305,40 +271,23 @@ int qr_svd_batched(const double* A, int m, int n, int batch, double* S, double* 
     if (!A || !S || n < 1 || n > QR_BATCHED_MAX_N || m < n || !qrd_b_fits(m, n) || batch < 0) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t mn = (size_t) m * n, nn = (size_t) n * n, nb = (size_t) batch;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, m, n, 0, 0));
-    double* d = NULL;
-    int* di = NULL;
-    int *dj = NULL, *drank = NULL, *dinfo = NULL;
-    double *dA = NULL, *dtau = NULL, *dS = NULL, *dU = NULL, *dV = NULL;
-    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (mn + 2 * (size_t) n + (U ? mn : 0) + (V ? nn : 0)));
-    if (!rc) {
-        dA = d; dtau = dA + nb * mn; dS = dtau + nb * (size_t) n;
-        double* next = dS + nb * (size_t) n;
-        if (U) { dU = next; next += nb * mn; }
-        if (V) dV = next;
-    }
-    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * ((size_t) n + 2));
-    if (!rc) { dj = di; drank = di + nb * (size_t) n; dinfo = drank + nb; }
     int* info = (int*) malloc(sizeof(int) * nb);
-    if (!rc && !info) rc = QR_E_ALLOC;
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
+    if (!info) return QR_E_ALLOC;
+    double *dA, *dtau, *dS, *dU, *dV;
+    int *dj, *drank, *dinfo;
+    /* U and V take no room where they are not wanted */
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dtau, nb * (size_t) n, NULL, NULL, 0),
+                         QR_STAGE_F64(dS, nb * (size_t) n, NULL, S, 0), QR_STAGE_F64(dU, U ? nb * mn : 0, NULL, U, 0),
+                         QR_STAGE_F64(dV, V ? nb * nn : 0, NULL, V, 0), QR_STAGE_I32(dj, nb * (size_t) n, NULL, NULL, 0),
+                         QR_STAGE_I32(drank, nb, NULL, rank, 0), QR_STAGE_I32(dinfo, nb, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m, n, t, QR_STAGE_COUNT(t));
     if (!rc)
-        rc = qr_gesvd_batched_dev(p, U ? 'U' : 'N', V ? 'V' : 'N', dA, m, n, m, (long long) mn, dj, n, dtau, n, dS, n, dU, m, (long long) mn, dV, n,
-                                  (long long) nn, drank, NULL, dinfo, batch);
-    if (!rc) rc = qrd_d2h(p->stream, S, dS, sizeof(double) * nb * (size_t) n);
-    if (!rc && U) rc = qrd_d2h(p->stream, U, dU, sizeof(double) * nb * mn);
-    if (!rc && V) rc = qrd_d2h(p->stream, V, dV, sizeof(double) * nb * nn);
-    if (!rc && rank) rc = qrd_d2h(p->stream, rank, drank, sizeof(int) * nb);
-    if (!rc) rc = qrd_d2h(p->stream, info, dinfo, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            if (info[q]) rc = QR_E_NOCONV;
+        rc = qr_gesvd_batched_dev(st.plan, U ? 'U' : 'N', V ? 'V' : 'N', dA, m, n, m, (long long) mn, dj, n, dtau, n, dS, n, U ? dU : NULL, m,
+                                  (long long) mn, V ? dV : NULL, n, (long long) nn, drank, NULL, dinfo, batch);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb)) rc = QR_E_NOCONV;
+    qr_stage_close(&st);
     free(info);
-    if (di) qrd_free(di);
-    if (d) qrd_free(d);
-    qr_plan_destroy(p);
     return rc;
 }

@@ -16,6 +16,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 /* 1 <= n <= 63, m >= n, and m rows are held */
 static int bad_shape(int m, int n)
@@ -47,47 +48,27 @@ int qr_bvls_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda, 
     return qrd_bv_solve(plan->stream, &a);
 }
 
-/* the host-pointer twin: a plan of its own, one device allocation of doubles and one of ints, packed batches */
+/* the host-pointer twin: packed batches, staged as qr_stage.h describes */
 int qr_lstsq_bounded_batched(const double* A, int m, int n, const double* b, const double* lo, const double* hi, int maxit, int batch, double* X,
                              double* W, int* state, double* resid, int* iter, int* info)
 {
     if (!A || !b || !X || !info || batch < 0 || bad_shape(m, n)) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t nb = (size_t) batch, mn = (size_t) m * n, nn = (size_t) n;
-    qr_plan* plan = NULL;
-    int rc = qr_plan_create(&plan, m, n, 0, 0);
-    if (rc) return rc;
-    double* dv = NULL;
-    int* di = NULL;
-    double *dA = NULL, *dB = NULL, *dlo = NULL, *dhi = NULL, *dX = NULL, *dW = NULL, *dres = NULL;
-    int *dstate = NULL, *diter = NULL, *dinfo = NULL;
-    rc = qrd_malloc((void**) &dv, sizeof(double) * nb * (mn + (size_t) m + 4 * nn + 1));
-    if (!rc) { dA = dv; dB = dA + nb * mn; dlo = dB + nb * m; dhi = dlo + nb * nn; dX = dhi + nb * nn; dW = dX + nb * nn; dres = dW + nb * nn; }
-    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * (nn + 2));
-    if (!rc) { dstate = di; diter = dstate + nb * nn; dinfo = diter + nb; }
-    if (!rc) rc = qrd_h2d(plan->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(plan->stream, dB, b, sizeof(double) * nb * m);
-    if (!rc && lo) rc = qrd_h2d(plan->stream, dlo, lo, sizeof(double) * nb * nn);
-    if (!rc && hi) rc = qrd_h2d(plan->stream, dhi, hi, sizeof(double) * nb * nn);
+    double *dA, *dB, *dlo, *dhi, *dX, *dW, *dres;
+    int *dstate, *diter, *dinfo;
     /* a member with info -1 or j + 1 has nothing written: its X, W, resid, state and iter read 0 */
-    if (!rc) rc = qrd_memset(plan->stream, dX, 0, sizeof(double) * nb * (2 * nn + 1));
-    if (!rc) rc = qrd_memset(plan->stream, di, 0, sizeof(int) * nb * (nn + 1));
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dB, nb * (size_t) m, b, NULL, 0), QR_STAGE_F64(dlo, nb * nn, lo, NULL, 0),
+                         QR_STAGE_F64(dhi, nb * nn, hi, NULL, 0), QR_STAGE_F64(dX, nb * nn, NULL, X, 1), QR_STAGE_F64(dW, nb * nn, NULL, W, 1),
+                         QR_STAGE_F64(dres, nb, NULL, resid, 1), QR_STAGE_I32(dstate, nb * nn, NULL, state, 1), QR_STAGE_I32(diter, nb, NULL, iter, 1),
+                         QR_STAGE_I32(dinfo, nb, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m, n, t, QR_STAGE_COUNT(t));
     if (!rc)
-        rc = qr_bvls_batched_dev(plan, dA, m, n, m, (long long) mn, dB, m, lo ? dlo : NULL, hi ? dhi : NULL, n, maxit, dX, n, W ? dW : NULL, n,
+        rc = qr_bvls_batched_dev(st.plan, dA, m, n, m, (long long) mn, dB, m, lo ? dlo : NULL, hi ? dhi : NULL, n, maxit, dX, n, W ? dW : NULL, n,
                                  state ? dstate : NULL, n, resid ? dres : NULL, iter ? diter : NULL, dinfo, batch);
-    if (!rc) rc = qrd_d2h(plan->stream, X, dX, sizeof(double) * nb * nn);
-    if (!rc && W) rc = qrd_d2h(plan->stream, W, dW, sizeof(double) * nb * nn);
-    if (!rc && resid) rc = qrd_d2h(plan->stream, resid, dres, sizeof(double) * nb);
-    if (!rc && state) rc = qrd_d2h(plan->stream, state, dstate, sizeof(int) * nb * nn);
-    if (!rc && iter) rc = qrd_d2h(plan->stream, iter, diter, sizeof(int) * nb);
-    if (!rc) rc = qrd_d2h(plan->stream, info, dinfo, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(plan->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            if (info[q]) rc = QR_E_SINGULAR;
-    if (di) qrd_free(di);
-    if (dv) qrd_free(dv);
-    qr_plan_destroy(plan);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb)) rc = QR_E_SINGULAR;
+    qr_stage_close(&st);
     return rc;
 }

@@ -20,6 +20,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 #define CHECK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
@@ -147,7 +148,7 @@ int qr_lsacc_batched_solve_damped_dev(qr_lsacc_batched* acc, const double* dD, l
     return qrd_bd_solve(acc->p->stream, &a);
 }
 
-/* the host-pointer twin: a plan of its own, one device allocation, packed batches */
+/* the host-pointer twin: packed batches, staged as qr_stage.h describes */
 int qr_lstsq_damped_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, const double* D, const double* lam, int nlam,
                             double* X, double* xnorm, double* resid, int* info)
 {
@@ -157,40 +158,25 @@ int qr_lstsq_damped_batched(const double* A, int m, int n, const double* B, int 
         return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t nb = (size_t) batch, mn = (size_t) m * n, mr = (size_t) m * nrhs, cols = (size_t) nlam * nrhs, nx = (size_t) n * cols;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, wide ? n : m, k, 0, 0));
-    double* d = NULL;
-    int* dinfo = NULL;
-    double *dA = NULL, *dF = NULL, *dB = NULL, *dtau = NULL, *dD = NULL, *dlam = NULL, *dX = NULL, *dxn = NULL, *dres = NULL;
-    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (2 * mn + mr + (size_t) k + (size_t) n + (size_t) nlam + nx + 2 * cols));
-    if (!rc) {
-        dA = d; dF = dA + nb * mn; dB = dF + nb * mn; dtau = dB + nb * mr; dD = dtau + nb * (size_t) k; dlam = dD + nb * (size_t) n;
-        dX = dlam + nb * (size_t) nlam; dxn = dX + nb * nx; dres = dxn + nb * cols;
-    }
-    if (!rc) rc = qrd_malloc((void**) &dinfo, sizeof(int) * nb * (size_t) nlam);
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(p->stream, dB, B, sizeof(double) * nb * mr);
-    if (!rc) rc = qrd_h2d(p->stream, dlam, lam, sizeof(double) * nb * (size_t) nlam);
-    if (!rc && D) rc = qrd_h2d(p->stream, dD, D, sizeof(double) * nb * (size_t) n);
+    double *dA, *dF, *dB, *dtau, *dD, *dlam, *dX, *dxn, *dres;
+    int* dinfo;
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dF, nb * mn, NULL, NULL, 0), QR_STAGE_F64(dB, nb * mr, B, NULL, 0),
+                         QR_STAGE_F64(dtau, nb * (size_t) k, NULL, NULL, 0), QR_STAGE_F64(dD, nb * (size_t) n, D, NULL, 0),
+                         QR_STAGE_F64(dlam, nb * (size_t) nlam, lam, NULL, 0), QR_STAGE_F64(dX, nb * nx, NULL, X, 0),
+                         QR_STAGE_F64(dxn, nb * cols, NULL, xnorm, 0), QR_STAGE_F64(dres, nb * cols, NULL, resid, 0),
+                         QR_STAGE_I32(dinfo, nb * (size_t) nlam, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, wide ? n : m, k, t, QR_STAGE_COUNT(t));
     if (!rc) {
         if (wide)
-            rc = qr_gels_damped_wide_batched_dev(p, dA, m, n, m, (long long) mn, dF, n, (long long) mn, dtau, m, dB, nrhs, m, (long long) mr, dlam,
-                                                 nlam, nlam, dX, n, (long long) nx, dxn, dres, dinfo, batch);
+            rc = qr_gels_damped_wide_batched_dev(st.plan, dA, m, n, m, (long long) mn, dF, n, (long long) mn, dtau, m, dB, nrhs, m, (long long) mr,
+                                                 dlam, nlam, nlam, dX, n, (long long) nx, dxn, dres, dinfo, batch);
         else
-            rc = qr_gels_damped_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dB, nrhs, m, (long long) mr, D ? dD : NULL, n, dlam, nlam,
-                                            nlam, dX, n, (long long) nx, dxn, dres, dinfo, batch);
+            rc = qr_gels_damped_batched_dev(st.plan, dA, m, n, m, (long long) mn, dtau, n, dB, nrhs, m, (long long) mr, D ? dD : NULL, n, dlam,
+                                            nlam, nlam, dX, n, (long long) nx, dxn, dres, dinfo, batch);
     }
-    if (!rc) rc = qrd_d2h(p->stream, X, dX, sizeof(double) * nb * nx);
-    if (!rc && xnorm) rc = qrd_d2h(p->stream, xnorm, dxn, sizeof(double) * nb * cols);
-    if (!rc && resid) rc = qrd_d2h(p->stream, resid, dres, sizeof(double) * nb * cols);
-    if (!rc) rc = qrd_d2h(p->stream, info, dinfo, sizeof(int) * nb * (size_t) nlam);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t i = 0; i < nb * (size_t) nlam; ++i)
-            if (info[i]) rc = QR_E_SINGULAR;
-    if (dinfo) qrd_free(dinfo);
-    if (d) qrd_free(d);
-    qr_plan_destroy(p);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb * (size_t) nlam)) rc = QR_E_SINGULAR;
+    qr_stage_close(&st);
     return rc;
 }

@@ -17,6 +17,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 /* 1 <= n <= 63, m >= n, and m rows are held */
 static int bad_shape(int m, int n)
@@ -71,7 +72,7 @@ int qr_gels_weighted_batched_dev(qr_plan* plan, const double* dA, int m, int n, 
                                strideX, NULL, 0, NULL, dresid, NULL, NULL, dinfo, batch);
 }
 
-/* the host-pointer twin: a plan of its own, one device allocation of doubles and one of ints, packed batches */
+/* the host-pointer twin: packed batches, staged as qr_stage.h describes */
 int qr_lstsq_robust_batched(const double* A, int m, int n, const double* b, int loss, double tune, const double* prior, const double* scale_in,
                             const double* x0, double tol, int maxit, int batch, double* X, double* W, double* scale, double* resid, int* iter,
                             int* status, int* info)
@@ -79,46 +80,21 @@ int qr_lstsq_robust_batched(const double* A, int m, int n, const double* b, int 
     if (!A || !b || !X || !info || batch < 0 || bad_control(loss, tune, tol) || bad_shape(m, n)) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t nb = (size_t) batch, mn = (size_t) m * n, nn = (size_t) n, mm = (size_t) m;
-    qr_plan* plan = NULL;
-    int rc = qr_plan_create(&plan, m, n, 0, 0);
-    if (rc) return rc;
-    double* dv = NULL;
-    int* di = NULL;
-    double *dA = NULL, *dB = NULL, *dP = NULL, *dS = NULL, *dX0 = NULL, *dX = NULL, *dW = NULL, *dsc = NULL, *dres = NULL;
-    int *diter = NULL, *dstat = NULL, *dinfo = NULL;
-    rc = qrd_malloc((void**) &dv, sizeof(double) * nb * (mn + 3 * mm + 2 * nn + 3));
-    if (!rc) {
-        dA = dv; dB = dA + nb * mn; dP = dB + nb * mm; dS = dP + nb * mm; dX0 = dS + nb;
-        dX = dX0 + nb * nn; dW = dX + nb * nn; dsc = dW + nb * mm; dres = dsc + nb;       /* the outputs: contiguous from dX */
-    }
-    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * 3);
-    if (!rc) { diter = di; dstat = diter + nb; dinfo = dstat + nb; }
-    if (!rc) rc = qrd_h2d(plan->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(plan->stream, dB, b, sizeof(double) * nb * mm);
-    if (!rc && prior) rc = qrd_h2d(plan->stream, dP, prior, sizeof(double) * nb * mm);
-    if (!rc && scale_in) rc = qrd_h2d(plan->stream, dS, scale_in, sizeof(double) * nb);
-    if (!rc && x0) rc = qrd_h2d(plan->stream, dX0, x0, sizeof(double) * nb * nn);
+    double *dA, *dB, *dP, *dS, *dX0, *dX, *dW, *dsc, *dres;
+    int *diter, *dstat, *dinfo;
     /* a member with an info word has nothing else written: its X, W, scale, resid, iter and status read 0 */
-    if (!rc) rc = qrd_memset(plan->stream, dX, 0, sizeof(double) * nb * (nn + mm + 2));
-    if (!rc) rc = qrd_memset(plan->stream, di, 0, sizeof(int) * nb * 2);
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dB, nb * mm, b, NULL, 0), QR_STAGE_F64(dP, nb * mm, prior, NULL, 0),
+                         QR_STAGE_F64(dS, nb, scale_in, NULL, 0), QR_STAGE_F64(dX0, nb * nn, x0, NULL, 0), QR_STAGE_F64(dX, nb * nn, NULL, X, 1),
+                         QR_STAGE_F64(dW, nb * mm, NULL, W, 1), QR_STAGE_F64(dsc, nb, NULL, scale, 1), QR_STAGE_F64(dres, nb, NULL, resid, 1),
+                         QR_STAGE_I32(diter, nb, NULL, iter, 1), QR_STAGE_I32(dstat, nb, NULL, status, 1), QR_STAGE_I32(dinfo, nb, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m, n, t, QR_STAGE_COUNT(t));
     if (!rc)
-        rc = qr_irls_batched_dev(plan, loss, tune, dA, m, n, m, (long long) mn, dB, m, prior ? dP : NULL, m, scale_in ? dS : NULL,
+        rc = qr_irls_batched_dev(st.plan, loss, tune, dA, m, n, m, (long long) mn, dB, m, prior ? dP : NULL, m, scale_in ? dS : NULL,
                                  x0 ? dX0 : NULL, n, tol, maxit, dX, n, W ? dW : NULL, m, scale ? dsc : NULL, resid ? dres : NULL,
                                  iter ? diter : NULL, status ? dstat : NULL, dinfo, batch);
-    if (!rc) rc = qrd_d2h(plan->stream, X, dX, sizeof(double) * nb * nn);
-    if (!rc && W) rc = qrd_d2h(plan->stream, W, dW, sizeof(double) * nb * mm);
-    if (!rc && scale) rc = qrd_d2h(plan->stream, scale, dsc, sizeof(double) * nb);
-    if (!rc && resid) rc = qrd_d2h(plan->stream, resid, dres, sizeof(double) * nb);
-    if (!rc && iter) rc = qrd_d2h(plan->stream, iter, diter, sizeof(int) * nb);
-    if (!rc && status) rc = qrd_d2h(plan->stream, status, dstat, sizeof(int) * nb);
-    if (!rc) rc = qrd_d2h(plan->stream, info, dinfo, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(plan->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            if (info[q]) rc = QR_E_SINGULAR;
-    if (di) qrd_free(di);
-    if (dv) qrd_free(dv);
-    qr_plan_destroy(plan);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb)) rc = QR_E_SINGULAR;
+    qr_stage_close(&st);
     return rc;
 }

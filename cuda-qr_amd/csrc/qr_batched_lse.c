@@ -15,6 +15,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 /* a block of `cols` columns of `rows` rows: columns at least `rows` apart, members at least ld * cols apart */
 static int bad_block(int rows, int cols, int ld, long long stride) { return ld < rows || stride < (long long) ld * cols; }
@@ -49,7 +50,7 @@ int qr_gglse_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda,
     return qrd_bl_solve(plan->stream, &a);
 }
 
-/* the host-pointer twin: a plan of its own, one device allocation, packed batches */
+/* the host-pointer twin: packed batches, staged as qr_stage.h describes */
 int qr_lstsq_constrained_batched(const double* A, int m, int n, const double* C, int p, const double* b, const double* d, int nrhs, int batch,
                                  double* X, double* L, double* resid, int* info)
 {
@@ -57,35 +58,19 @@ int qr_lstsq_constrained_batched(const double* A, int m, int n, const double* C,
     if (batch == 0) return 0;
     const size_t nb = (size_t) batch, mn = (size_t) m * n, pn = (size_t) p * n, mr = (size_t) m * nrhs, pr = (size_t) p * nrhs,
                  nr = (size_t) n * nrhs;
-    qr_plan* plan = NULL;
-    int rc = qr_plan_create(&plan, m > n ? m : n, n, 0, 0);
-    if (rc) return rc;
-    double* dv = NULL;
-    int* dinfo = NULL;
-    double *dA = NULL, *dC = NULL, *dB = NULL, *dD = NULL, *dX = NULL, *dL = NULL, *dres = NULL;
-    rc = qrd_malloc((void**) &dv, sizeof(double) * nb * (mn + pn + mr + pr + nr + pr + (size_t) nrhs));
-    if (!rc) { dA = dv; dC = dA + nb * mn; dB = dC + nb * pn; dD = dB + nb * mr; dX = dD + nb * pr; dL = dX + nb * nr; dres = dL + nb * pr; }
-    if (!rc) rc = qrd_malloc((void**) &dinfo, sizeof(int) * nb);
-    if (!rc) rc = qrd_h2d(plan->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(plan->stream, dC, C, sizeof(double) * nb * pn);
-    if (!rc) rc = qrd_h2d(plan->stream, dB, b, sizeof(double) * nb * mr);
-    if (!rc) rc = qrd_h2d(plan->stream, dD, d, sizeof(double) * nb * pr);
+    double *dA, *dC, *dB, *dD, *dX, *dL, *dres;
+    int* dinfo;
     /* a member with an info word has nothing written: its X, L and resid read 0 */
-    if (!rc) rc = qrd_memset(plan->stream, dX, 0, sizeof(double) * nb * (nr + pr + (size_t) nrhs));
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dC, nb * pn, C, NULL, 0), QR_STAGE_F64(dB, nb * mr, b, NULL, 0),
+                         QR_STAGE_F64(dD, nb * pr, d, NULL, 0), QR_STAGE_F64(dX, nb * nr, NULL, X, 1), QR_STAGE_F64(dL, nb * pr, NULL, L, 1),
+                         QR_STAGE_F64(dres, nb * (size_t) nrhs, NULL, resid, 1), QR_STAGE_I32(dinfo, nb, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m > n ? m : n, n, t, QR_STAGE_COUNT(t));
     if (!rc)
-        rc = qr_gglse_batched_dev(plan, dA, m, n, m, (long long) mn, dC, p, p, (long long) pn, dB, m, (long long) mr, dD, p, (long long) pr, nrhs,
+        rc = qr_gglse_batched_dev(st.plan, dA, m, n, m, (long long) mn, dC, p, p, (long long) pn, dB, m, (long long) mr, dD, p, (long long) pr, nrhs,
                                   dX, n, (long long) nr, L ? dL : NULL, p, (long long) pr, resid ? dres : NULL, nrhs, dinfo, batch);
-    if (!rc) rc = qrd_d2h(plan->stream, X, dX, sizeof(double) * nb * nr);
-    if (!rc && L) rc = qrd_d2h(plan->stream, L, dL, sizeof(double) * nb * pr);
-    if (!rc && resid) rc = qrd_d2h(plan->stream, resid, dres, sizeof(double) * nb * (size_t) nrhs);
-    if (!rc) rc = qrd_d2h(plan->stream, info, dinfo, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(plan->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            if (info[q]) rc = QR_E_SINGULAR;
-    if (dinfo) qrd_free(dinfo);
-    if (dv) qrd_free(dv);
-    qr_plan_destroy(plan);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb)) rc = QR_E_SINGULAR;
+    qr_stage_close(&st);
     return rc;
 }

@@ -18,6 +18,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 /* 1 <= n <= 63, 1 <= mg <= 64, 0 <= neq <= min(n, mg), m >= 1, m + neq >= n, and m rows are held */
 static int bad_shape(int m, int n, int mg, int neq)
@@ -55,49 +56,28 @@ int qr_lsei_batched_dev(qr_plan* plan, const double* dA, int m, int n, int lda, 
     return qrd_le_solve(plan->stream, &a);
 }
 
-/* the host-pointer twin: a plan of its own, one device allocation of doubles and one of ints, packed batches */
+/* the host-pointer twin: packed batches, staged as qr_stage.h describes */
 int qr_lstsq_inequality_batched(const double* A, int m, int n, const double* b, const double* G, int mg, int neq, const double* h, int maxit,
                                 double rcond, int batch, double* X, double* MU, double* S, int* state, double* resid, int* iter, int* info)
 {
     if (!A || !b || !G || !h || !X || !info || batch < 0 || bad_shape(m, n, mg, neq)) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t nb = (size_t) batch, mn = (size_t) m * n, gn = (size_t) mg * n, nn = (size_t) n, gg = (size_t) mg;
-    qr_plan* plan = NULL;
-    int rc = qr_plan_create(&plan, m > n ? m : n, n, 0, 0);
-    if (rc) return rc;
-    double* dv = NULL;
-    int* di = NULL;
-    double *dA = NULL, *dB = NULL, *dG = NULL, *dH = NULL, *dX = NULL, *dMU = NULL, *dS = NULL, *dres = NULL;
-    int *dstate = NULL, *diter = NULL, *dinfo = NULL;
-    rc = qrd_malloc((void**) &dv, sizeof(double) * nb * (mn + (size_t) m + gn + gg + nn + 2 * gg + 1));
-    if (!rc) { dA = dv; dB = dA + nb * mn; dG = dB + nb * m; dH = dG + nb * gn; dX = dH + nb * gg; dMU = dX + nb * nn; dS = dMU + nb * gg; dres = dS + nb * gg; }
-    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * (gg + 2));
-    if (!rc) { dstate = di; diter = dstate + nb * gg; dinfo = diter + nb; }
-    if (!rc) rc = qrd_h2d(plan->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(plan->stream, dB, b, sizeof(double) * nb * m);
-    if (!rc) rc = qrd_h2d(plan->stream, dG, G, sizeof(double) * nb * gn);
-    if (!rc) rc = qrd_h2d(plan->stream, dH, h, sizeof(double) * nb * gg);
+    double *dA, *dB, *dG, *dH, *dX, *dMU, *dS, *dres;
+    int *dstate, *diter, *dinfo;
     /* a member with info -2, -3 or i + 1 has nothing written: its X, MU, S, resid, state and iter read 0 */
-    if (!rc) rc = qrd_memset(plan->stream, dX, 0, sizeof(double) * nb * (nn + 2 * gg + 1));
-    if (!rc) rc = qrd_memset(plan->stream, di, 0, sizeof(int) * nb * (gg + 1));
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dB, nb * (size_t) m, b, NULL, 0), QR_STAGE_F64(dG, nb * gn, G, NULL, 0),
+                         QR_STAGE_F64(dH, nb * gg, h, NULL, 0), QR_STAGE_F64(dX, nb * nn, NULL, X, 1), QR_STAGE_F64(dMU, nb * gg, NULL, MU, 1),
+                         QR_STAGE_F64(dS, nb * gg, NULL, S, 1), QR_STAGE_F64(dres, nb, NULL, resid, 1), QR_STAGE_I32(dstate, nb * gg, NULL, state, 1),
+                         QR_STAGE_I32(diter, nb, NULL, iter, 1), QR_STAGE_I32(dinfo, nb, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m > n ? m : n, n, t, QR_STAGE_COUNT(t));
     if (!rc)
-        rc = qr_lsei_batched_dev(plan, dA, m, n, m, (long long) mn, dB, m, dG, mg, neq, mg, (long long) gn, dH, mg, maxit, rcond, dX, n,
+        rc = qr_lsei_batched_dev(st.plan, dA, m, n, m, (long long) mn, dB, m, dG, mg, neq, mg, (long long) gn, dH, mg, maxit, rcond, dX, n,
                                  MU ? dMU : NULL, mg, S ? dS : NULL, mg, state ? dstate : NULL, mg, resid ? dres : NULL, iter ? diter : NULL,
                                  dinfo, batch);
-    if (!rc) rc = qrd_d2h(plan->stream, X, dX, sizeof(double) * nb * nn);
-    if (!rc && MU) rc = qrd_d2h(plan->stream, MU, dMU, sizeof(double) * nb * gg);
-    if (!rc && S) rc = qrd_d2h(plan->stream, S, dS, sizeof(double) * nb * gg);
-    if (!rc && resid) rc = qrd_d2h(plan->stream, resid, dres, sizeof(double) * nb);
-    if (!rc && state) rc = qrd_d2h(plan->stream, state, dstate, sizeof(int) * nb * gg);
-    if (!rc && iter) rc = qrd_d2h(plan->stream, iter, diter, sizeof(int) * nb);
-    if (!rc) rc = qrd_d2h(plan->stream, info, dinfo, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(plan->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            if (info[q]) rc = QR_E_SINGULAR;
-    if (di) qrd_free(di);
-    if (dv) qrd_free(dv);
-    qr_plan_destroy(plan);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb)) rc = QR_E_SINGULAR;
+    qr_stage_close(&st);
     return rc;
 }

@@ -19,6 +19,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 #define CHECK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
@@ -96,41 +97,29 @@ int qr_gels_wide_batched_dev(qr_plan* p, const double* dA, int m, int n, int lda
     return qrd_bm_apply(p->stream, dF, n, m, ldf, sf, dtau, st, dB, nrhs, ldb, sb, dinfo, batch);
 }
 
-/* the host-pointer twin: a plan of its own, one device allocation, packed batches */
+/* the host-pointer twin: packed batches, staged as qr_stage.h describes */
 int qr_lstsq_minnorm_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, double* X, int* info)
 {
     if (!A || !B || !X || !info || bad_wide_shape(m, n) || nrhs < 1 || batch < 0) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t mn = (size_t) m * n, nr = (size_t) n * nrhs, nb = (size_t) batch;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, n, m, 0, 0));
-    double* d = NULL;
-    int* dinfo = NULL;
-    double *dA = NULL, *dF = NULL, *dB = NULL, *dtau = NULL;
-    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (2 * mn + nr + (size_t) m));
-    if (!rc) { dA = d; dF = dA + nb * mn; dB = dF + nb * mn; dtau = dB + nb * nr; }
-    if (!rc) rc = qrd_malloc((void**) &dinfo, sizeof(int) * nb);
     /* X doubles as the staging image of dB: B on top of n - m rows of zeros per column */
+    for (size_t q = 0; q < nb; ++q)
+        for (int j = 0; j < nrhs; ++j) {
+            double* c = X + (q * nrhs + j) * n;
+            memcpy(c, B + (q * nrhs + j) * m, sizeof(double) * (size_t) m);
+            memset(c + m, 0, sizeof(double) * (size_t) (n - m));
+        }
+    double *dA, *dF, *dB, *dtau;
+    int* dinfo;
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dF, nb * mn, NULL, NULL, 0), QR_STAGE_F64(dB, nb * nr, X, X, 0),
+                         QR_STAGE_F64(dtau, nb * (size_t) m, NULL, NULL, 0), QR_STAGE_I32(dinfo, nb, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, n, m, t, QR_STAGE_COUNT(t));
     if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            for (int j = 0; j < nrhs; ++j) {
-                double* c = X + (q * nrhs + j) * n;
-                memcpy(c, B + (q * nrhs + j) * m, sizeof(double) * (size_t) m);
-                memset(c + m, 0, sizeof(double) * (size_t) (n - m));
-            }
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(p->stream, dB, X, sizeof(double) * nb * nr);
-    if (!rc)
-        rc = qr_gels_wide_batched_dev(p, dA, m, n, m, (long long) mn, dF, n, (long long) mn, dtau, m, dB, nrhs, n, (long long) nr, dinfo, batch);
-    if (!rc) rc = qrd_d2h(p->stream, X, dB, sizeof(double) * nb * nr);
-    if (!rc) rc = qrd_d2h(p->stream, info, dinfo, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            if (info[q]) rc = QR_E_SINGULAR;
-    if (dinfo) qrd_free(dinfo);
-    if (d) qrd_free(d);
-    qr_plan_destroy(p);
+        rc = qr_gels_wide_batched_dev(st.plan, dA, m, n, m, (long long) mn, dF, n, (long long) mn, dtau, m, dB, nrhs, n, (long long) nr, dinfo, batch);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb)) rc = QR_E_SINGULAR;
+    qr_stage_close(&st);
     return rc;
 }

@@ -19,6 +19,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 /* the fused fit: 1 <= n <= 63, m >= n, and m rows are held */
 static int bad_shape(int m, int n)
@@ -107,52 +108,28 @@ int qr_lsacc_batched_covar_dev(qr_lsacc_batched* acc, int scaled, int rhs, doubl
     return qrd_bs_covar(acc->p->stream, &a);
 }
 
-/* the host-pointer twin: a plan of its own, one device allocation of doubles and one of ints, packed batches */
+/* the host-pointer twin: packed batches, staged as qr_stage.h describes */
 int qr_lstsq_stats_batched(const double* A, int m, int n, const double* b, const double* prior, int scaled, int batch, double* X, double* E,
                            double* H, double* sigma2, int* dof, double* Cov, double* se, int* info)
 {
     if (!A || !b || !X || !info || batch < 0 || (scaled != QR_COV_UNSCALED && scaled != QR_COV_SCALED) || bad_shape(m, n)) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t nb = (size_t) batch, mn = (size_t) m * n, nn = (size_t) n, mm = (size_t) m;
-    qr_plan* plan = NULL;
-    int rc = qr_plan_create(&plan, m, n, 0, 0);
-    if (rc) return rc;
-    double* dv = NULL;
-    int* di = NULL;
-    double *dA = NULL, *dB = NULL, *dP = NULL, *dX = NULL, *dE = NULL, *dH = NULL, *dsig = NULL, *dC = NULL, *dse = NULL;
-    int *ddof = NULL, *dinfo = NULL;
-    rc = qrd_malloc((void**) &dv, sizeof(double) * nb * (mn + 4 * mm + 2 * nn + nn * nn + 1));
-    if (!rc) {
-        dA = dv; dB = dA + nb * mn; dP = dB + nb * mm;
-        dX = dP + nb * mm; dE = dX + nb * nn; dH = dE + nb * mm; dsig = dH + nb * mm; dC = dsig + nb; dse = dC + nb * nn * nn;   /* the outputs: contiguous from dX */
-    }
-    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * 2);
-    if (!rc) { ddof = di; dinfo = ddof + nb; }
-    if (!rc) rc = qrd_h2d(plan->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(plan->stream, dB, b, sizeof(double) * nb * mm);
-    if (!rc && prior) rc = qrd_h2d(plan->stream, dP, prior, sizeof(double) * nb * mm);
+    double *dA, *dB, *dP, *dX, *dE, *dH, *dsig, *dC, *dse;
+    int *ddof, *dinfo;
     /* a member with an info word has nothing else written: its outputs read 0 */
-    if (!rc) rc = qrd_memset(plan->stream, dX, 0, sizeof(double) * nb * (2 * nn + 2 * mm + nn * nn + 1));
-    if (!rc) rc = qrd_memset(plan->stream, di, 0, sizeof(int) * nb);
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dB, nb * mm, b, NULL, 0), QR_STAGE_F64(dP, nb * mm, prior, NULL, 0),
+                         QR_STAGE_F64(dX, nb * nn, NULL, X, 1), QR_STAGE_F64(dE, nb * mm, NULL, E, 1), QR_STAGE_F64(dH, nb * mm, NULL, H, 1),
+                         QR_STAGE_F64(dsig, nb, NULL, sigma2, 1), QR_STAGE_F64(dC, nb * nn * nn, NULL, Cov, 1), QR_STAGE_F64(dse, nb * nn, NULL, se, 1),
+                         QR_STAGE_I32(ddof, nb, NULL, dof, 1), QR_STAGE_I32(dinfo, nb, NULL, info, 0) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, m, n, t, QR_STAGE_COUNT(t));
     if (!rc)
-        rc = qr_gels_stats_batched_dev(plan, scaled, dA, m, n, m, (long long) mn, dB, m, prior ? dP : NULL, m, dX, n, E ? dE : NULL, m,
+        rc = qr_gels_stats_batched_dev(st.plan, scaled, dA, m, n, m, (long long) mn, dB, m, prior ? dP : NULL, m, dX, n, E ? dE : NULL, m,
                                        H ? dH : NULL, m, sigma2 ? dsig : NULL, dof ? ddof : NULL, Cov ? dC : NULL, n, (long long) (nn * nn),
                                        se ? dse : NULL, n, dinfo, batch);
-    if (!rc) rc = qrd_d2h(plan->stream, X, dX, sizeof(double) * nb * nn);
-    if (!rc && E) rc = qrd_d2h(plan->stream, E, dE, sizeof(double) * nb * mm);
-    if (!rc && H) rc = qrd_d2h(plan->stream, H, dH, sizeof(double) * nb * mm);
-    if (!rc && sigma2) rc = qrd_d2h(plan->stream, sigma2, dsig, sizeof(double) * nb);
-    if (!rc && Cov) rc = qrd_d2h(plan->stream, Cov, dC, sizeof(double) * nb * nn * nn);
-    if (!rc && se) rc = qrd_d2h(plan->stream, se, dse, sizeof(double) * nb * nn);
-    if (!rc && dof) rc = qrd_d2h(plan->stream, dof, ddof, sizeof(int) * nb);
-    if (!rc) rc = qrd_d2h(plan->stream, info, dinfo, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(plan->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t q = 0; q < nb; ++q)
-            if (info[q]) rc = QR_E_SINGULAR;
-    if (di) qrd_free(di);
-    if (dv) qrd_free(dv);
-    qr_plan_destroy(plan);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb)) rc = QR_E_SINGULAR;
+    qr_stage_close(&st);
     return rc;
 }

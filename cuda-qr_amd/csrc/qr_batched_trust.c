@@ -21,6 +21,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 #define CHECK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
@@ -155,7 +156,7 @@ int qr_lsacc_batched_solve_trust_dev(qr_lsacc_batched* acc, const double* dD, lo
     return qrd_bt_solve(acc->p->stream, &a);
 }
 
-/* the host-pointer twin: a plan of its own, one device allocation, packed batches */
+/* the host-pointer twin: packed batches, staged as qr_stage.h describes */
 int qr_lstsq_trust_batched(const double* A, int m, int n, const double* b, int batch, const double* D, const double* delta, const double* lam0,
                            double rtol, int maxit, double* X, double* lam, double* xnorm, double* resid, int* iter, int* status, int* info)
 {
@@ -164,45 +165,26 @@ int qr_lstsq_trust_batched(const double* A, int m, int n, const double* b, int b
     if (wide ? (D != NULL || bad_wide_shape(m, n)) : (n > QR_BATCHED_MAX_N - 1 || !qrd_b_fits(m, n))) return QR_E_ARG;
     if (batch == 0) return 0;
     const size_t nb = (size_t) batch, mn = (size_t) m * n;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, wide ? n : m, k, 0, 0));
-    double* d = NULL;
-    int* di = NULL;
-    double *dA = NULL, *dF = NULL, *dB = NULL, *dtau = NULL, *dD = NULL, *ddel = NULL, *dl0 = NULL, *dX = NULL, *dlam = NULL, *dxn = NULL, *dres = NULL;
-    int rc = qrd_malloc((void**) &d, sizeof(double) * nb * (2 * mn + (size_t) m + (size_t) k + 2 * (size_t) n + 5));
-    if (!rc) {
-        dA = d; dF = dA + nb * mn; dB = dF + nb * mn; dtau = dB + nb * (size_t) m; dD = dtau + nb * (size_t) k; dX = dD + nb * (size_t) n;
-        ddel = dX + nb * (size_t) n; dl0 = ddel + nb; dlam = dl0 + nb; dxn = dlam + nb; dres = dxn + nb;
-    }
-    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * nb * 3);
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(p->stream, dB, b, sizeof(double) * nb * (size_t) m);
-    if (!rc) rc = qrd_h2d(p->stream, ddel, delta, sizeof(double) * nb);
-    if (!rc && lam0) rc = qrd_h2d(p->stream, dl0, lam0, sizeof(double) * nb);
-    if (!rc && D) rc = qrd_h2d(p->stream, dD, D, sizeof(double) * nb * (size_t) n);
-    if (!rc) rc = qrd_memset(p->stream, di, 0, sizeof(int) * nb * 3);    /* iter and status of a member with an info word read 0 */
+    double *dA, *dF, *dB, *dtau, *dD, *dX, *ddel, *dl0, *dlam, *dxn, *dres;
+    int *diter, *dstat, *dinfo;
+    /* iter and status of a member with an info word read 0 */
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dF, nb * mn, NULL, NULL, 0), QR_STAGE_F64(dB, nb * (size_t) m, b, NULL, 0),
+                         QR_STAGE_F64(dtau, nb * (size_t) k, NULL, NULL, 0), QR_STAGE_F64(dD, nb * (size_t) n, D, NULL, 0),
+                         QR_STAGE_F64(dX, nb * (size_t) n, NULL, X, 0), QR_STAGE_F64(ddel, nb, delta, NULL, 0), QR_STAGE_F64(dl0, nb, lam0, NULL, 0),
+                         QR_STAGE_F64(dlam, nb, NULL, lam, 0), QR_STAGE_F64(dxn, nb, NULL, xnorm, 0), QR_STAGE_F64(dres, nb, NULL, resid, 0),
+                         QR_STAGE_I32(diter, nb, NULL, iter, 1), QR_STAGE_I32(dstat, nb, NULL, status, 1), QR_STAGE_I32(dinfo, nb, NULL, info, 1) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, wide ? n : m, k, t, QR_STAGE_COUNT(t));
     if (!rc) {
         if (wide)
-            rc = qr_gels_trust_wide_batched_dev(p, dA, m, n, m, (long long) mn, dF, n, (long long) mn, dtau, m, dB, m, m, ddel, 1,
-                                                lam0 ? dl0 : NULL, 1, rtol, maxit, dX, n, n, dlam, dxn, dres, di, di + nb, di + 2 * nb, batch);
+            rc = qr_gels_trust_wide_batched_dev(st.plan, dA, m, n, m, (long long) mn, dF, n, (long long) mn, dtau, m, dB, m, m, ddel, 1,
+                                                lam0 ? dl0 : NULL, 1, rtol, maxit, dX, n, n, dlam, dxn, dres, diter, dstat, dinfo, batch);
         else
-            rc = qr_gels_trust_batched_dev(p, dA, m, n, m, (long long) mn, dtau, n, dB, m, m, D ? dD : NULL, n, ddel, 1, lam0 ? dl0 : NULL, 1,
-                                           rtol, maxit, dX, n, n, dlam, dxn, dres, di, di + nb, di + 2 * nb, batch);
+            rc = qr_gels_trust_batched_dev(st.plan, dA, m, n, m, (long long) mn, dtau, n, dB, m, m, D ? dD : NULL, n, ddel, 1, lam0 ? dl0 : NULL, 1,
+                                           rtol, maxit, dX, n, n, dlam, dxn, dres, diter, dstat, dinfo, batch);
     }
-    if (!rc) rc = qrd_d2h(p->stream, X, dX, sizeof(double) * nb * (size_t) n);
-    if (!rc) rc = qrd_d2h(p->stream, lam, dlam, sizeof(double) * nb);
-    if (!rc && xnorm) rc = qrd_d2h(p->stream, xnorm, dxn, sizeof(double) * nb);
-    if (!rc && resid) rc = qrd_d2h(p->stream, resid, dres, sizeof(double) * nb);
-    if (!rc && iter) rc = qrd_d2h(p->stream, iter, di, sizeof(int) * nb);
-    if (!rc && status) rc = qrd_d2h(p->stream, status, di + nb, sizeof(int) * nb);
-    if (!rc) rc = qrd_d2h(p->stream, info, di + 2 * nb, sizeof(int) * nb);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
-    if (!rc)
-        for (size_t i = 0; i < nb; ++i)
-            if (info[i]) rc = QR_E_SINGULAR;
-    if (di) qrd_free(di);
-    if (d) qrd_free(d);
-    qr_plan_destroy(p);
+    rc = qr_stage_fetch(&st, rc);
+    if (!rc && qr_stage_any(info, nb)) rc = QR_E_SINGULAR;
+    qr_stage_close(&st);
     return rc;
 }

@@ -18,6 +18,7 @@
 #include "../../include/mi355x_qr.h"
 #include "qr_device.h"
 #include "qr_plan_internal.h"
+#include "qr_stage.h"
 
 #define CHECK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
@@ -226,7 +227,7 @@ int qr_lsacc_batched_solve_dev(qr_lsacc_batched* a, double* dX, int ldx, long lo
     return qrd_b_trsm(s, a->R, a->n, a->n, (size_t) a->n * a->n, dX, a->nrhs, ldx, (size_t) strideX, dinfo, a->batch);
 }
 
-/* ---- the host-pointer twin ---- */
+/* ---- the host-pointer twin: staged as qr_stage.h describes; the accumulator borrows the stage's plan ---- */
 int qr_lstsq_rolling_batched(const double* A, int m, int n, const double* B, int nrhs, int batch, int window, int step, double* X,
                              double* resid, int* info)
 {
@@ -236,21 +237,16 @@ int qr_lstsq_rolling_batched(const double* A, int m, int n, const double* B, int
     if (batch == 0) return 0;
     const size_t nwin = (size_t) ((m - window) / step + 1), nb = (size_t) batch, nx = (size_t) n * nrhs;
     const size_t mn = (size_t) m * n, mr = (size_t) m * nrhs;
-    qr_plan* p = NULL;
-    CHECK(qr_plan_create(&p, window, n, 0, 0));
-    qr_lsacc_batched* a = NULL;
-    double* d = NULL;
-    int* di = NULL;
-    double *dA = NULL, *dB = NULL, *dX = NULL, *dres = NULL;
     int* hi = (int*) malloc(sizeof(int) * 2 * nwin * nb);
-    int rc = hi ? 0 : QR_E_ALLOC;
-    if (!rc) rc = qr_lsacc_batched_create(&a, p, n, nrhs, batch);
-    if (!rc) rc = qrd_malloc((void**) &d, sizeof(double) * nb * (mn + mr + nwin * (nx + (size_t) nrhs)));
-    if (!rc) { dA = d; dB = dA + nb * mn; dX = dB + nb * mr; dres = dX + nb * nwin * nx; }
-    if (!rc) rc = qrd_malloc((void**) &di, sizeof(int) * 2 * nwin * nb);
-    if (!rc) rc = qrd_memset(p->stream, di, 0, sizeof(int) * 2 * nwin * nb);
-    if (!rc) rc = qrd_h2d(p->stream, dA, A, sizeof(double) * nb * mn);
-    if (!rc) rc = qrd_h2d(p->stream, dB, B, sizeof(double) * nb * mr);
+    if (!hi) return QR_E_ALLOC;
+    qr_lsacc_batched* a = NULL;
+    double *dA, *dB, *dX, *dres;
+    int* di;
+    qr_stage_buf t[] = { QR_STAGE_F64(dA, nb * mn, A, NULL, 0), QR_STAGE_F64(dB, nb * mr, B, NULL, 0), QR_STAGE_F64(dX, nb * nwin * nx, NULL, X, 0),
+                         QR_STAGE_F64(dres, nb * nwin * (size_t) nrhs, NULL, resid, 0), QR_STAGE_I32(di, 2 * nwin * nb, NULL, hi, 1) };
+    qr_stage st;
+    int rc = qr_stage_open(&st, window, n, t, QR_STAGE_COUNT(t));
+    if (!rc) rc = qr_lsacc_batched_create(&a, st.plan, n, nrhs, batch);
     /* di: window k's update words at [k * batch, ..), its solve words nwin * batch further on */
     for (size_t k = 0; !rc && k < nwin; ++k) {
         if (k == 0) rc = qr_lsacc_batched_push_dev(a, dA, window, m, (long long) mn, dB, m, (long long) mr);
@@ -263,11 +259,7 @@ int qr_lstsq_rolling_batched(const double* A, int m, int n, const double* B, int
             rc = qr_lsacc_batched_solve_dev(a, dX + k * nx, n, (long long) (nwin * nx), dres + k * (size_t) nrhs,
                                             (long long) (nwin * (size_t) nrhs), di + (nwin + k) * nb);
     }
-    if (!rc) rc = qrd_d2h(p->stream, X, dX, sizeof(double) * nb * nwin * nx);
-    if (!rc && resid) rc = qrd_d2h(p->stream, resid, dres, sizeof(double) * nb * nwin * (size_t) nrhs);
-    if (!rc) rc = qrd_d2h(p->stream, hi, di, sizeof(int) * 2 * nwin * nb);
-    const int rs = qrd_stream_sync(p->stream);
-    if (!rc) rc = rs;
+    rc = qr_stage_fetch(&st, rc);
     if (!rc) {
         int notpd = 0, sing = 0;
         for (size_t q = 0; q < nb; ++q)
@@ -280,9 +272,7 @@ int qr_lstsq_rolling_batched(const double* A, int m, int n, const double* B, int
         rc = notpd ? QR_E_NOTPD : (sing ? QR_E_SINGULAR : 0);
     }
     if (a) qr_lsacc_batched_destroy(a);
-    if (di) qrd_free(di);
-    if (d) qrd_free(d);
+    qr_stage_close(&st);
     free(hi);
-    qr_plan_destroy(p);
     return rc;
 }

@@ -165,7 +165,9 @@ def test_strerror_names_rccl_failures(qr):
 def test_host_layer_under_sanitizers(target):
     """SURVEY section 5 (race detection / sanitizers): the C host layer (schedule, plan cache, per-device threads of
     qr_thin_mgpu, TSQR plan) built with AddressSanitizer + UBSan / ThreadSanitizer against the test-only stub device layer
-    (tests/c/qrd_stub.c bounds-checks every operand block a launch receives) and run through tests/c/host_sanitize.c."""
+    (tests/c/qrd_stub.c bounds-checks every operand block a launch receives) and run through tests/c/host_sanitize.c.  The same
+    targets build and run cuda-qr_amd/tools/stage_sanitize.c over the staging unit of the batched host-pointer twins (csrc/qr_stage.c): the carve
+    of its one allocation, every copy and clear inside it, the error path, an overflowing table, no leak."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if not k.startswith("MI355XQR_")}
     out = subprocess.run(["make", "-C", os.path.join(root, "cuda-qr_amd"), target], capture_output=True, text=True, env=env, timeout=600)
