@@ -41,7 +41,7 @@ int qrd_tn_even_last_grid(void);            /* workgroups of the last one */
 /* Kernel tests only: the route the last call of qrd_gemm_nn, qrd_gemm_nn_update / _update2, qrd_gemm_tn / _tn_update (/ _wide / _even),
  * qrd_gemm_nn_batch or qrd_slab_reduce took, written by the launch functions where they decide (one record for the process; a call that
  * returns before it launches anything leaves the record cleared but for the entry and the serial).  Returns the serial.
- *   out[0] entry: 1 nn, 2 nn_update, 3 tn, 4 nn_batch, 5 slab_reduce          out[1] tile TI TJ as two digits (44, 41, 22, 11, 14)
+ *   out[0] entry: 1 nn, 2 nn_update, 3 tn, 4 nn_batch, 5 slab_reduce, 6 nt (qrd_gemm_nt)      out[1] tile TI TJ as two digits (44, 41, 22, 11, 14; nt: 42, 44)
  *   out[2], out[3] the fast interior Mi, Ni (0, 0: one guarded launch over everything; MIXED: the whole M, N)
  *   out[4] ksplit (slabs summed, for slab_reduce; workgroups, for the even split)      out[5] row piece of the reduction (0: none ran)
  *   out[6] flag bits (QRD_ROUTE_*)                                            out[7] serial number of the record */
@@ -53,7 +53,14 @@ int qrd_tn_even_last_grid(void);            /* workgroups of the last one */
 #define QRD_ROUTE_TM 32         /* Tm folded in by the reduction */
 #define QRD_ROUTE_DIRECT 64     /* no slabs: the product kernel wrote C itself */
 #define QRD_ROUTE_W8 128        /* gemm_nn_w8_kernel on the interior */
+#define QRD_ROUTE_KEEP 256      /* gemm_nt4_kernel<.., KEEP>: the K loop's barrier leaves the tile two ahead in flight */
 int qrd_gemm_last_route(int out[8]);
+/* qrd_gemm_nt's record, kept apart so that the products a factorisation runs after its last wide update do not wipe it: the same eight
+ * fields, entry 6 (nt), tile 42 (gemm_nt4_kernel, 128 x 64) or 44 (gemm_nt_kernel), out[2], out[3] the M, N of the call, out[7] the
+ * number of qrd_gemm_nt launches so far in this process */
+#define QRD_ROUTE_ENTRY_NT 6
+int qrd_gemm_nt_last_route(int out[8]);
+void qrd_gemm_route_note(int entry, int tile, int Mi, int Ni, int flags);     /* qr_gemm_nt.hip -> the records of qr_kernels.hip */
 /* second-generation wide update (qr_gemm_nt.hip): W kept transposed, direct-to-LDS tile loads */
 int qrd_gemm2_init(void);
 int qrd_gemm_nt_ok(int M, int N, int K, const double* A, int lda, const double* Bt, int ldbt, const double* C, int ldc);

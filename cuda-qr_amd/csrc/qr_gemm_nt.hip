@@ -270,12 +270,30 @@ __global__ __launch_bounds__(512, 4) void gemm_nt_kernel(int M, int N, int K, co
 // of 128 (qrd_gemm_nt4_ok: that fits A's leading dimension -- the rows are whatever the buffer holds and only reach accumulators that
 // are never stored).  What it is for: outer blocks of 64 columns, where every other trailing matrix starts 64 rows into a tile and the
 // update went to the generic kernels (4096^2 at nb 64: 0.20 against 0.15 ms per step), and matrices whose height is not a multiple of 128.
-template <bool NEG, int CEIL, int BK4, int NS, bool RAG = false>
+// KEEP (round 26): the K loop's barrier leaves the tile two ahead in flight.  The loop was written that way from the start (s_waitcnt
+// vmcnt(3) in front of the barrier), but the barrier was s_barrier between a release and an acquire fence over the local address space,
+// and a direct-to-LDS load both counts in vmcnt and writes LDS: the compiler turns the release into s_waitcnt vmcnt(0) right behind the
+// hand-written vmcnt(3) (visible in the disassembly), so every barrier drained the load queue and the third stage bought nothing.  KEEP
+// spells out what the barrier needs instead: this wave's share of the next stage has landed (vmcnt(3): only the three newest loads stay
+// in flight), its reads of the current stage have returned (lgkmcnt(0); they have anyway, the MFMAs in front consumed them), and neither
+// the compiler ("memory" clobbers) nor the scheduler (sched_barrier) moves an LDS access across the s_barrier.  Isolated on CUs
+// [32, 256) at 16384 x 16128 x 256: 56.5 against 53.9 TFLOP/s; in situ 52.2 against 50.5 (profiles/r26_nt_late_c.txt).  KEEP = false
+// (the fenced barrier) is instantiated in the lab build only: MI355XQR_NT_KEEP=0.
+// (Round 26, measured and removed: LATE C -- accumulators from zero, the prologue waiting for operand stage 0 alone, the C tile fetched
+// as per-lane 16-byte granules behind the last operand tile: six of a lane's sixteen by global_load_lds into wave-private 1 KB slots of
+// the two ring stages that are free under the last two k-tiles, the other ten into the dead fragment registers right behind the loop,
+// C + acc stored.  That avoids both limits of the earlier attempts (no VGPRs under the loop, no C load in front of an operand load in the
+// in-order vmcnt queue) and was correct, at 121 VGPRs and four workgroups per CU -- and ran at 54.8 isolated and 50.7 in situ: above the
+// draining parent only through this barrier, and 3 % BELOW the same barrier with C through the accumulators.  The two k-tiles that have
+// a free stage last 1.7 us, less than a C round trip under load, and only 24 of the tile's 64 KB fit; the rest is a second exposed round
+// trip at the end, where the form above pays one at the start that it shares with the first operand tiles.)
+template <bool NEG, int CEIL, int BK4, int NS, bool RAG = false, bool KEEP = false>
 __global__ __launch_bounds__(256, (BK4 == 8 ? 4 : 3)) void gemm_nt4_kernel(int M, int N, int K, const double* __restrict__ A, int lda,
                                                           const double* __restrict__ Bt, int ldbt,
                                                           double* __restrict__ C, int ldc, int gx, int gy, int gm)
 {
     // BK4 = 8, NS = 3: 36 KB of LDS, four workgroups per CU, tiles two ahead;  BK4 = 16, NS = 2: 48 KB, three per CU, tiles one ahead
+    static_assert(!KEEP || (BK4 == 8 && NS == 3), "KEEP: the three-stage kernel's spelled-out K loop");
     constexpr int STAGE = BK4 * 128 + BK4 * 64;           // doubles per stage: A image [BK4][128] + B image [BK4][64]
     constexpr int NLD = 3 * BK4 / 8;                       // tile-load instructions per wave and stage
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -361,11 +379,18 @@ __global__ __launch_bounds__(256, (BK4 == 8 ? 4 : 3)) void gemm_nt4_kernel(int M
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) { mm(1, j); N4_SB; }     // step 1 (set 1), first half
-            if (more) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+            if constexpr (KEEP) {
+                if (more) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");      // the tile two ahead stays in flight
+                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            } else {
+                if (more) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");     // (drains the load queue: see KEEP)
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+            }
             N4_SB;
 #pragma unroll
             for (int j = 4; j < 8; ++j) {                        // second half, over the next stage's first fragment reads (set 0 is free)
@@ -439,6 +464,16 @@ static int nt_ceil(void)
 #endif
 
 
+// MI355XQR_NT_KEEP=0 (lab build only): the four-workgroup kernel with the fenced barrier that drains the load queue, as it was before
+// round 26 -- one session can A/B the two (profiles/r26_nt_late_c.txt).  The product library has the KEEP form alone.
+#ifdef QR_LAB
+static int nt_keep(void)
+{
+    static const int v = QRD_LAB_ENV_INT("MI355XQR_NT_KEEP", 1);
+    return v;
+}
+#endif
+
 static int nt_gm(void)
 {
     static const int v = 8;     // read once, thread-safe
@@ -463,9 +498,11 @@ int qrd_gemm2_init(void)
     rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<false, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * NT_STAGE * 8);
     rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * NT_STAGE * 8);
     rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<true, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
+    rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt4_kernel<true, 0, 8, 3, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 8 * 192 * 8);
+    rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt4_kernel<true, 0, 8, 3, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 8 * 192 * 8);
+#ifdef QR_LAB
     rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt4_kernel<true, 0, 8, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 8 * 192 * 8);
     rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt4_kernel<true, 0, 8, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 8 * 192 * 8);
-#ifdef QR_LAB
     rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<true, 0, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
     rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<true, 0, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
     rc |= (int) hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt4_kernel<true, 1, 8, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 8 * 192 * 8);
@@ -476,6 +513,21 @@ int qrd_gemm2_init(void)
 #endif
     return rc;
 }
+
+#ifdef QR_LAB
+// workgroups of gemm_nt4_kernel<true, 0, 8, 3, rag, keep> the runtime keeps resident on a compute unit (devtools/tools_nt_lab.py: must be 4)
+int qrd_gemm_nt4_occupancy(int rag, int keep)
+{
+    int n = -1;
+    const size_t shm = 3 * (8 * 192) * sizeof(double);
+    hipError_t e;
+    if (keep) e = rag ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_nt4_kernel<true, 0, 8, 3, true, true>, 256, shm)
+                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_nt4_kernel<true, 0, 8, 3, false, true>, 256, shm);
+    else e = rag ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_nt4_kernel<true, 0, 8, 3, true, false>, 256, shm)
+                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_nt4_kernel<true, 0, 8, 3, false, false>, 256, shm);
+    return e == hipSuccess ? n : -(int) e;
+}
+#endif
 
 // 1 if (M, N, K, operands) can go to gemm_nt_kernel as they are
 int qrd_gemm_nt_ok(int M, int N, int K, const double* A, int lda, const double* Bt, int ldbt, const double* C, int ldc)
@@ -501,12 +553,18 @@ int qrd_gemm_nt(void* stream, int M, int N, int K, int sign, const double* A, in
         // N = 64 (mod 128) and / or M = 64 (mod 128): the four-workgroup kernel alone
         const int gx4 = (M + 127) / 128, gy4 = N / 64;
         if (gm < 0) gm = nt_gm();
-        if (M % 128)
-            hipLaunchKernelGGL((gemm_nt4_kernel<true, 0, 8, 3, true>), dim3(gx4 * gy4), dim3(256), 3 * (8 * 192) * sizeof(double), (hipStream_t) stream,
-                               M, N, K, A, lda, Bt, ldbt, C, ldc, gx4, gy4, gm);
-        else
-            hipLaunchKernelGGL((gemm_nt4_kernel<true, 0, 8, 3>), dim3(gx4 * gy4), dim3(256), 3 * (8 * 192) * sizeof(double), (hipStream_t) stream,
-                               M, N, K, A, lda, Bt, ldbt, C, ldc, gx4, gy4, gm);
+#define NT4_HALF(RAG, KEEP) hipLaunchKernelGGL((gemm_nt4_kernel<true, 0, 8, 3, RAG, KEEP>), dim3(gx4 * gy4), dim3(256), 3 * (8 * 192) * sizeof(double), \
+                                               (hipStream_t) stream, M, N, K, A, lda, Bt, ldbt, C, ldc, gx4, gy4, gm)
+#ifdef QR_LAB
+        if (!nt_keep()) {
+            if (M % 128) NT4_HALF(true, false); else NT4_HALF(false, false);
+            qrd_gemm_route_note(QRD_ROUTE_ENTRY_NT, 42, M, N, 0);
+            return (int) hipGetLastError();
+        }
+#endif
+        if (M % 128) NT4_HALF(true, true); else NT4_HALF(false, true);
+#undef NT4_HALF
+        qrd_gemm_route_note(QRD_ROUTE_ENTRY_NT, 42, M, N, QRD_ROUTE_KEEP);
         return (int) hipGetLastError();
     }
     if (!qrd_gemm_nt_ok(M, N, K, A, lda, Bt, ldbt, C, ldc)) return -7;
@@ -520,14 +578,19 @@ int qrd_gemm_nt(void* stream, int M, int N, int K, int sign, const double* A, in
         // four workgroups per CU (k-tiles of 8, three stages)
         const int gy4 = N / 64;
         const dim3 g(gx * gy4), b(256);
-#define NT4_LAUNCH(CE, BK, NS) hipLaunchKernelGGL((gemm_nt4_kernel<true, CE, BK, NS>), g, b, NS * (BK * 192) * sizeof(double), s, M, N, K, A, lda, Bt, ldbt, C, ldc, gx, gy4, gm)
+#define NT4_LAUNCH(CE, BK, NS, KEEP) hipLaunchKernelGGL((gemm_nt4_kernel<true, CE, BK, NS, false, KEEP>), g, b, NS * (BK * 192) * sizeof(double), s, M, N, K, A, lda, Bt, ldbt, C, ldc, gx, gy4, gm)
+        int keep = QRD_ROUTE_KEEP;
 #ifdef QR_LAB
-        if (nt4() == 2) { if (nt_ceil() == 1) NT4_LAUNCH(1, 16, 2); else if (nt_ceil() == 2) NT4_LAUNCH(2, 16, 2); else NT4_LAUNCH(0, 16, 2); }
-        else { if (nt_ceil() == 1) NT4_LAUNCH(1, 8, 3); else if (nt_ceil() == 2) NT4_LAUNCH(2, 8, 3); else NT4_LAUNCH(0, 8, 3); }
+        if (nt4() == 2) { keep = 0; if (nt_ceil() == 1) NT4_LAUNCH(1, 16, 2, false); else if (nt_ceil() == 2) NT4_LAUNCH(2, 16, 2, false); else NT4_LAUNCH(0, 16, 2, false); }
+        else if (nt_ceil() == 1) { keep = 0; NT4_LAUNCH(1, 8, 3, false); }
+        else if (nt_ceil() == 2) { keep = 0; NT4_LAUNCH(2, 8, 3, false); }
+        else if (!nt_keep()) { keep = 0; NT4_LAUNCH(0, 8, 3, false); }
+        else NT4_LAUNCH(0, 8, 3, true);
 #else
-        NT4_LAUNCH(0, 8, 3);
+        NT4_LAUNCH(0, 8, 3, true);
 #endif
 #undef NT4_LAUNCH
+        qrd_gemm_route_note(QRD_ROUTE_ENTRY_NT, 42, M, N, keep);
         return (int) hipGetLastError();
     }
 #ifdef QR_LAB
@@ -540,6 +603,7 @@ int qrd_gemm_nt(void* stream, int M, int N, int K, int sign, const double* A, in
         return (int) hipGetLastError();
     }
 #endif
+    qrd_gemm_route_note(QRD_ROUTE_ENTRY_NT, 44, M, N, 0);
     if (stamps)
         hipLaunchKernelGGL((gemm_nt_kernel<true, 1>), dim3(gx * gy), dim3(512), shm, s, M, N, K, A, lda, Bt, ldbt, C, ldc, gx, gy, gm, stamps);
     else if (sign < 0 && nt_il())

@@ -418,11 +418,12 @@ static int plan_create_impl(qr_plan** out, int m, int n, int nb, int ib, int tsq
         p->bal_rp = 14.0; p->bal_ru = 44.0; p->bal_tc0 = 1.1; p->bal_tc1 = 0.6;
         if (p->npairs) {            /* measured ~0.22 TFLOP/s per CU for the K = 256 update GEMMs on either side of the partition; the update
                                      * stream's pair Wt = A2^T (V T), A2 -= V Wt^T at 16384^2 since the even K split of the first: 57.8 and 50.9
-                                     * TFLOP/s in situ on 224 CUs, i.e. 54.1 for the pair = 0.242 per CU (0.23 before; profiles/NOTES.md) */
+                                     * TFLOP/s in situ on 224 CUs, i.e. 54.1 for the pair = 0.242 per CU (0.23 before); since the update's
+                                     * barrier stopped draining its load queue 57.4 and 52.2, i.e. 54.7 = 0.244 per CU (profiles/NOTES.md) */
             int cus = 256;
             qrd_device_info(NULL, 0, &cus, NULL, NULL);
             const int pc = qrd_stream_cus(p->s_pair[0][0]);
-            p->bal_rp = 0.22 * pc; p->bal_ru = 0.242 * (cus - pc);
+            p->bal_rp = 0.22 * pc; p->bal_ru = 0.244 * (cus - pc);
         }
         if (b) {
             p->bal_rp = 0.0;
@@ -1276,7 +1277,7 @@ static int enter_phase(qr_plan* p, int i)
         const int pc = qrd_stream_cus(ns);
         const int uc = nu ? qrd_stream_cus(nu) : cus;
         p->bal_rp = 0.22 * (pc < cus ? pc : 32);
-        p->bal_ru = 0.242 * uc;
+        p->bal_ru = 0.244 * uc;
         const double f = pc <= 32 ? 1.0 : (pc <= 64 ? 0.8 : 0.7);
         p->bal_tc0 = p->bal_tc0_base * f; p->bal_tc1 = p->bal_tc1_base * f;
     }

@@ -1230,6 +1230,21 @@ int qrd_gemm_last_route(int out[8])
     for (int f = 0; f < 8; ++f) out[f] = g_route[f].load(std::memory_order_relaxed);
     return out[ROUTE_SERIAL];
 }
+// qrd_gemm_nt (qr_gemm_nt.hip) leaves its route in the record above and in one of its own, which later products of other entries leave alone
+static std::atomic<int> g_route_nt[8];
+void qrd_gemm_route_note(int entry, int tile, int Mi, int Ni, int flags)
+{
+    route_begin(entry);
+    route_tiles(tile, Mi, Ni, flags);
+    const int at[5] = {ROUTE_ENTRY, ROUTE_TILE, ROUTE_MI, ROUTE_NI, ROUTE_FLAGS}, v[5] = {entry, tile, Mi, Ni, flags};
+    for (int f = 0; f < 5; ++f) g_route_nt[at[f]].store(v[f], std::memory_order_relaxed);
+    g_route_nt[ROUTE_SERIAL].fetch_add(1, std::memory_order_relaxed);
+}
+int qrd_gemm_nt_last_route(int out[8])
+{
+    for (int f = 0; f < 8; ++f) out[f] = g_route_nt[f].load(std::memory_order_relaxed);
+    return out[ROUTE_SERIAL];
+}
 
 // Modelled cost, in K rows of one workgroup slot like the split-K rule's, of the even split on G workgroups: every workgroup walks
 // ceil(U / G) k-tiles; it pays the fixed cost of a launch's workgroup once and a partial-tile store plus an operand prologue for
