@@ -225,6 +225,30 @@ _sig("qr_lsei_batched_dev", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, _
      C.c_double, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, C.c_int)
 _sig("qr_lstsq_inequality_batched", C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp,
      _ip, _dp, _ip, _ip)
+class LmOptions(C.Structure):
+    """qr_lm_options"""
+    _fields_ = [("ftol", C.c_double), ("xtol", C.c_double), ("gtol", C.c_double), ("factor", C.c_double), ("par_rtol", C.c_double),
+                ("maxfev", C.c_int), ("mode", C.c_int), ("par_maxit", C.c_int)]
+
+
+class LmState(C.Structure):
+    """qr_lm_batched_state: device addresses"""
+    _doubles = ("x", "xtrial", "D", "delta", "par", "fnorm", "xnorm", "pnorm", "gnorm", "prered", "dirder")
+    _ints = ("iter", "nfev", "njev", "accepted", "status", "info", "par_status")
+    _fields_ = [(k, C.c_void_p) for k in _doubles + _ints]
+
+
+LM_FCN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, _dp, C.c_int, _dp, _dp)
+_sig("qr_lm_options_default", None, C.POINTER(LmOptions))
+_sig("qr_lm_batched_create", C.c_int, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmOptions))
+_sig("qr_lm_batched_start_dev", C.c_int, _vp, _vp, C.c_int, _ll, _vp, _ll)
+_sig("qr_lm_batched_step_dev", C.c_int, _vp, _vp, C.c_int, _ll, _vp, C.c_int, _ll)
+_sig("qr_lm_batched_update_dev", C.c_int, _vp, _vp, C.c_int, _ll)
+_sig("qr_lm_batched_view", C.c_int, _vp, C.POINTER(LmState))
+_sig("qr_lm_batched_running", C.c_int, _vp, C.POINTER(C.c_int))
+_sig("qr_lm_batched_destroy", C.c_int, _vp)
+_sig("qr_lm_step_batched_dev", C.c_int, _vp, _vp, C.c_int, _ll, _vp, C.c_int, C.c_int, _ll, _vp, _vp, _ll)
+_sig("qr_lstsq_lm_batched", C.c_int, LM_FCN, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(LmOptions), _dp, _ip, _ip, _ip, _ip)
 _sig("qr_irls_batched_max_rows", C.c_int, C.c_int)
 _sig("qr_irls_batched_dev", C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _ll, C.c_double,
      C.c_int, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -926,6 +950,66 @@ def lstsq_inequality_batched(A, b, G, h, neq=0, maxit=0, rcond=0.0):
     return X, mu, s, state[:batch].astype(np.int64), resid, it[:batch].astype(np.int64), info[:batch].astype(np.int64)
 
 
+LM_OPTION_NAMES = tuple(k for k, _ in LmOptions._fields_)
+
+
+def lm_options(**options):
+    """qr_lm_options: MINPACK lmder1's defaults (qr_lm_options_default) with the given fields replaced"""
+    o = LmOptions()
+    lib.qr_lm_options_default(C.byref(o))
+    for k, v in options.items():
+        if k not in LM_OPTION_NAMES:
+            raise QRError(f"lm options: unknown option {k!r} (known: {', '.join(LM_OPTION_NAMES)})", QR_E_ARG)
+        setattr(o, k, v)
+    return o
+
+
+def lstsq_lm_batched(fun, jac, x0, D=None, m=None, **options):
+    """min ||f_q(x)|| for every member by Levenberg-Marquardt (MINPACK lmder's iteration, the loop of every member on the device) through
+    qr_lstsq_lm_batched.  fun: numpy (batch, n) -> (batch, m); jac: (batch, n) -> (batch, m, n); x0: (batch, n); D: the scaling of mode 2
+    (n,) or (batch, n); m: the number of residuals (None: fun is called once on x0 to find it); options: the fields of qr_lm_options.
+    Returns (X, fnorm, nfev, njev, status, info): status is MINPACK's info (1 .. 8), or -1 for a member with an info word (which does
+    not raise)."""
+    x0 = np.asarray(x0, dtype=np.float64)
+    if x0.ndim != 2:
+        raise QRError(f"lstsq_lm_batched: x0 must be (batch, n), got {x0.shape}", QR_E_ARG)
+    batch, n = x0.shape
+    if m is None:
+        m = int(np.asarray(fun(x0)).shape[1]) if batch else n
+    o = lm_options(**options)
+    if D is not None:
+        D = np.asarray(D, dtype=np.float64)
+        if D.ndim == 1:
+            D = np.broadcast_to(D, (batch, D.shape[0]))
+        if D.shape != (batch, n):
+            raise QRError(f"lstsq_lm_batched: D must be ({n},) or ({batch}, {n}), got {D.shape}", QR_E_ARG)
+        D = np.ascontiguousarray(D)
+    raised = []
+
+    def model(_user, what, X, nb, F, J):
+        try:
+            Xn = np.ctypeslib.as_array(X, shape=(nb, n))
+            if what == 2:
+                np.ctypeslib.as_array(J, shape=(nb, n, m))[...] = np.asarray(jac(Xn), dtype=np.float64).reshape(nb, m, n).transpose(0, 2, 1)
+            else:
+                np.ctypeslib.as_array(F, shape=(nb, m))[...] = np.asarray(fun(Xn), dtype=np.float64).reshape(nb, m)
+            return 0
+        except Exception as e:      # (an exception must not cross the C frames)
+            raised.append(e)
+            return QR_E_ARG
+
+    X = np.ascontiguousarray(x0).copy()
+    fnorm = np.zeros(batch)
+    nfev, njev, status, info = (np.zeros(max(batch, 1), dtype=np.intc) for _ in range(4))
+    rc = lib.qr_lstsq_lm_batched(LM_FCN(model), None, m, n, batch, _p(X), None if D is None else _p(D), C.byref(o), _p(fnorm),
+                                 nfev.ctypes.data_as(_ip), njev.ctypes.data_as(_ip), status.ctypes.data_as(_ip), info.ctypes.data_as(_ip))
+    if raised:
+        raise raised[0]
+    if rc != QR_E_SINGULAR:
+        check(rc, "qr_lstsq_lm_batched")
+    return X, fnorm, nfev[:batch].astype(np.int64), njev[:batch].astype(np.int64), status[:batch].astype(np.int64), info[:batch].astype(np.int64)
+
+
 QR_LOSS_LS, QR_LOSS_HUBER, QR_LOSS_BISQUARE = 0, 1, 2
 _LOSSES = {"ls": QR_LOSS_LS, "huber": QR_LOSS_HUBER, "bisquare": QR_LOSS_BISQUARE}
 
@@ -1425,6 +1509,15 @@ class Plan:
                                       strideH, int(maxit), float(rcond), _dptr(dX), strideX, _dptr(dMU), strideMU, _dptr(dS), strideS,
                                       _dptr(dstate), stridestate, _dptr(dresid), _dptr(diter), _dptr(dinfo), batch), "qr_lsei_batched_dev")
 
+    def lm_step_batched(self, lm, dR, ldr, strideR, dZ, zrows, ldz, strideZ, drss=None, djpvt=None, stridejpvt=0):
+        """the Levenberg-Marquardt step of every running member of the LmBatched `lm` (created on this plan) from factors that exist, in
+        LmBatched.step's place in the protocol: dR (n x n), dZ (the top zrows >= n rows of Q^T f), drss (the squares of the rows that are
+        not there, one per member), djpvt (int32, n per member) as for trust_batched"""
+        if lm.plan is not self:
+            raise QRError("lm_step_batched: the solver was created on another plan", QR_E_ARG)
+        check(lib.qr_lm_step_batched_dev(lm.h, _dptr(dR), ldr, strideR, _dptr(dZ), zrows, ldz, strideZ, _dptr(drss), _dptr(djpvt), stridejpvt),
+              "qr_lm_step_batched_dev")
+
     def irls_batched(self, loss, dA, m, n, lda, strideA, dB, strideB, dX, strideX, dinfo, batch, tune=0.0, dprior=None, strideprior=0,
                      dscale_in=None, dX0=None, strideX0=0, tol=1e-8, maxit=0, dW=None, strideW=0, dscale=None, dresid=None, diter=None,
                      dstatus=None):
@@ -1756,6 +1849,144 @@ class LsAccumulatorBatched:
 
     def reset(self):
         check(lib.qr_lsacc_batched_reset(self.h), "qr_lsacc_batched_reset")
+
+
+class _RawDeviceArray:
+    """zero-copy torch view of device memory the library owns, through __cuda_array_interface__"""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+class LmBatched:
+    """qr_lm_batched wrapper: MINPACK lmder's outer loop for every member of a batch, by reverse communication (mi355x_qr.h section 8m).
+    start(dX0); then per round: fill J and f at state()["x"], step(dJ, dF); fill f at state()["xtrial"], update(dFtrial); running()
+    is the one call that waits on the host.  The calls run on the plan's stream: model code in torch runs there too inside
+    `with torch.cuda.stream(torch.cuda.ExternalStream(plan.stream))`.  The plan must stay open for as long as the solver is used."""
+
+    def __init__(self, plan, m, n, batch, **options):
+        self.h = None
+        self.options = lm_options(**options)
+        h = _vp()
+        check(lib.qr_lm_batched_create(C.byref(h), plan.h, m, n, batch, C.byref(self.options)), "qr_lm_batched_create")
+        self.h, self.plan, self.m, self.n, self.batch = h, plan, m, n, batch
+        self._views = None
+
+    def close(self):
+        if self.h and lib is not None and self.plan.h:
+            lib.qr_lm_batched_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def start(self, dX0, ldx=None, strideX=None, dD0=None, strideD=None):
+        """x <- dX0 (n per member, packed unless ldx / strideX say otherwise); dD0: the scaling of mode 2 (strideD 0: shared)"""
+        ldx = self.n if ldx is None else ldx
+        check(lib.qr_lm_batched_start_dev(self.h, _dptr(dX0), ldx, ldx if strideX is None else strideX, _dptr(dD0),
+                                          self.n if strideD is None else strideD), "qr_lm_batched_start_dev")
+
+    def step(self, dJ, dF, ldj=None, strideJ=None, ldf=None, strideF=None):
+        """dJ (m x n per member, column-major) <- its pivoted factors, dF (m per member) <- Q^T f, then the step of every running member"""
+        ldj = self.m if ldj is None else ldj
+        ldf = self.m if ldf is None else ldf
+        check(lib.qr_lm_batched_step_dev(self.h, _dptr(dJ), ldj, ldj * self.n if strideJ is None else strideJ, _dptr(dF), ldf,
+                                         ldf if strideF is None else strideF), "qr_lm_batched_step_dev")
+
+    def update(self, dFtrial, ldf=None, strideF=None):
+        """dFtrial (m per member): f at the trial points"""
+        ldf = self.m if ldf is None else ldf
+        check(lib.qr_lm_batched_update_dev(self.h, _dptr(dFtrial), ldf, ldf if strideF is None else strideF), "qr_lm_batched_update_dev")
+
+    def view(self):
+        """the device addresses of the state: a dict of ints"""
+        v = LmState()
+        check(lib.qr_lm_batched_view(self.h, C.byref(v)), "qr_lm_batched_view")
+        return {k: getattr(v, k) for k, _ in LmState._fields_}
+
+    def state(self, device=None):
+        """the state as zero-copy torch views: x, xtrial, D (batch, n) float64; delta, par, fnorm, xnorm, pnorm, gnorm, prered, dirder
+        (batch,) float64; iter, nfev, njev, accepted, status, info, par_status (batch,) int32.  Read-only for the caller; reading them on
+        the host needs the plan's stream synchronised (running() does)."""
+        import torch
+        if self._views is None:
+            dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+            ptr = self.view()
+            out = {}
+            for k in LmState._doubles + LmState._ints:
+                shape = (self.batch, self.n) if k in ("x", "xtrial", "D") else (self.batch,)
+                if self.batch == 0:
+                    out[k] = torch.empty(shape, dtype=torch.float64 if k in LmState._doubles else torch.int32, device=dev)
+                else:
+                    out[k] = torch.as_tensor(_RawDeviceArray(ptr[k], shape, "<f8" if k in LmState._doubles else "<i4"), device=dev)
+            self._views = out
+        return self._views
+
+    def running(self):
+        """the number of members with status == 0 and info == 0; waits for the plan's stream"""
+        c = C.c_int()
+        check(lib.qr_lm_batched_running(self.h, C.byref(c)), "qr_lm_batched_running")
+        return c.value
+
+
+def lm_batched(fun, jac, x0, *, D=None, check_every=1, plan=None, **options):
+    """min ||f_q(x)|| for every member by Levenberg-Marquardt with the model in torch: fun maps x (batch, n) to f (batch, m) and jac to
+    J (batch, m, n), both on device tensors; x0: (batch, n) on the device; D: the scaling of mode 2, (n,) or (batch, n).  The model runs
+    on the plan's stream between the two device calls of a round, the wrapper does the layout copy of J, and running() -- the only host
+    wait -- is polled every `check_every` rounds.  options: the fields of qr_lm_options.  Returns a dict of torch tensors: the state of
+    LmBatched.state() (copies), x first."""
+    import torch
+    if x0.dim() != 2:
+        raise QRError(f"lm_batched: x0 must be (batch, n), got {tuple(x0.shape)}", QR_E_ARG)
+    batch, n = x0.shape
+    if D is not None:
+        options.setdefault("mode", 2)
+        D = torch.as_tensor(D, dtype=torch.float64, device=x0.device)
+        if D.dim() == 1:
+            D = D.expand(batch, n)
+        if tuple(D.shape) != (batch, n):
+            raise QRError(f"lm_batched: D must be ({n},) or ({batch}, {n}), got {tuple(D.shape)}", QR_E_ARG)
+        D = D.contiguous()
+    torch.cuda.synchronize()                  # x0 and D were made on torch's streams; from here on everything runs on the plan's
+    x0 = x0.to(torch.float64).contiguous()
+    m = int(fun(x0).shape[1])
+    torch.cuda.synchronize()
+    own = plan is None
+    if own:
+        plan = Plan(max(m, 1), n)
+    try:
+        return _lm_batched_run(plan, fun, jac, x0, D, m, max(int(check_every), 1), options)
+    finally:                                  # (whatever was allocated under the plan's stream is gone before the stream is)
+        torch.cuda.synchronize()
+        if own:
+            plan.close()
+
+
+def _lm_batched_run(plan, fun, jac, x0, D, m, every, options):
+    import torch
+    batch, n = x0.shape
+    lm = LmBatched(plan, m, n, batch, **options)
+    try:
+        J = torch.empty((batch, n, m), dtype=torch.float64, device=x0.device)           # member q: J_q column-major
+        F = torch.empty((batch, m), dtype=torch.float64, device=x0.device)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(torch.cuda.ExternalStream(plan.stream)):
+            lm.start(x0, dD0=D)
+            st = lm.state(x0.device)
+            limit = lm.options.maxfev if lm.options.maxfev > 0 else 100 * (n + 1)     # every round adds 1 to nfev of every running member
+            for rounds in range(1, limit + 1 if batch else 1):
+                J.copy_(jac(st["x"]).transpose(1, 2))
+                F.copy_(fun(st["x"]))
+                lm.step(J, F)
+                F.copy_(fun(st["xtrial"]))
+                lm.update(F)
+                if rounds % every == 0 and lm.running() == 0:
+                    break
+            plan.sync()
+        torch.cuda.synchronize()
+        return {k: v.clone() for k, v in st.items()}          # copies on the caller's stream: they outlive the solver and the plan
+    finally:
+        torch.cuda.synchronize()
+        lm.close()
 
 
 class TsqrPlan:

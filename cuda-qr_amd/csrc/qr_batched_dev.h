@@ -1,7 +1,7 @@
 // qr_batched_dev.h -- the device code that the batched kernel files (qr_batched.hip, qr_batched_update.hip, qr_batched_minnorm.hip,
 // qr_batched_svd.hip, qr_batched_damped.hip, qr_batched_trust.hip, qr_batched_lse.hip, qr_batched_bvls.hip, qr_batched_irls.hip, qr_batched_stats.hip, qr_batched_lsei.hip) share: the wave helpers, the dlarfg scalars, the Householder column step of the wave route and of the workgroup
 // route, one reflector on a column in registers, the triangular solves over an LDS image, the info word, the elimination of a damping block (shared by the damped and the
-// trust-region kernels), and the LDS opt-in.  No
+// trust-region kernels; the search itself, which qr_batched_lm.hip runs as well, is qr_batched_trust_dev.h), and the LDS opt-in.  No
 // kernels, no entry points.  Two kernels that call the same step here run the same operations in the same order: that is what makes
 // the factors and tau of qrd_b_geqrf, qrd_b_geqp3 (on the permuted columns) and qrd_bm_fused equal bit for bit on the same route.
 //

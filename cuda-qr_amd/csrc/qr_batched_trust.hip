@@ -20,99 +20,17 @@
 //
 // A column with d == 0 contributes nothing to the gradient bound g (its quotient is not formed); what the elimination then finds on
 // the diagonal decides its info word as in section 8f.
-#include <cfloat>
-
-#include "qr_batched_dev.h"
+#include "qr_batched_trust_dev.h"
 
 static_assert(QRD_B_MAX_N == 64, "one lane per row of the triangle");
 
-// a radius the search can run on
-__device__ __forceinline__ bool bt_delta_ok(double delta) { return delta > 0.0 && delta <= DBL_MAX; }
-
-// the bounds and the start of the iteration from the Gauss-Newton step (the same values in every thread): fp > rtol * delta on entry
-struct bt_state {
-    double par, parl, paru, fp;
-};
-
-// wnorm: |w| with R^T w = D^2 x / |D x| when R has full rank, else unused
-__device__ __forceinline__ void bt_start(bt_state& S, bool fullrank, double wnorm, double gnorm, double dxnorm, double delta, double lam0)
-{
-    S.parl = fullrank ? ((S.fp / delta) / wnorm) / wnorm : 0.0;
-    S.paru = gnorm / delta;
-    if (S.paru == 0.0) S.paru = DBL_MIN / fmin(delta, 0.1);
-    S.par = fmin(fmax(lam0 * lam0, S.parl), S.paru);
-    if (S.par == 0.0) S.par = gnorm / dxnorm;
-}
-
-// after an elimination and its solve: 0, 1 (never here), 2, 3, or -1 to go on
-__device__ __forceinline__ int bt_leave(const bt_state& S, double fpprev, double delta, double rtol, int it, int maxit)
-{
-    if (fabs(S.fp) <= rtol * delta) return 0;
-    if (S.parl == 0.0 && S.fp <= fpprev && fpprev < 0.0) return 2;
-    if (it >= maxit) return 3;
-    return -1;
-}
-
-// the Newton correction: wnorm = |w| with R~^T w = D^2 x / |D x|
-__device__ __forceinline__ void bt_update(bt_state& S, double wnorm, double delta)
-{
-    const double parc = ((S.fp / delta) / wnorm) / wnorm;
-    if (S.fp > 0.0) S.parl = fmax(S.parl, S.par);
-    if (S.fp < 0.0) S.paru = fmin(S.paru, S.par);
-    S.par = fmax(S.parl, S.par + parc);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// wave route.  r[]: lane i < n holds row i of the master [R | z] (z in column n), zeros below the diagonal and in lanes >= n.  Rs: this
-// wave's image of the triangle (W x (W + 1) doubles); Xs: x, then W + 1 doubles on, the vector of the forward substitution.
-// ---------------------------------------------------------------------------------------------------------------------------------
-
-// the triangle (columns < n of w) into Rs and column n, rows < rows, into Xs (zeros from there to n); lane 0 solves the leading block
-template <int W>
-__device__ __forceinline__ double bt_wave_solve(const double (&w)[W], int n, int rows, int lane, double* Rs, double* Xs)
-{
-    constexpr int LW = W + 1;
-#pragma unroll
-    for (int c = 0; c < W; ++c) {
-        if (c < n) {
-            if (lane < n) Rs[c * LW + lane] = w[c];
-        } else if (c == n) {
-            if (lane < n) Xs[lane] = lane < rows ? w[c] : 0.0;
-        }
-    }
-    QB_WAVE_SYNC();
-    if (lane == 0) qb_trsv(Rs, LW, rows, Xs);
-    QB_WAVE_SYNC();
-    return lane < n ? Xs[lane] : 0.0;
-}
-
-// |D x| as bd_wave_lams forms it
-__device__ __forceinline__ double bt_wave_dxnorm(double dsc, double xi)
-{
-    const double dx = dsc * xi;
-    return sqrt(bd_wave_dot(dx, dx));
-}
-
-// |w|, R^T w = D (D x / |D x|) over the image in Rs
-template <int W>
-__device__ __forceinline__ double bt_wave_wnorm(int n, int lane, double dsc, double xi, double dxnorm, const double* Rs, double* Us)
-{
-    constexpr int LW = W + 1;
-    if (lane < n) Us[lane] = dsc * ((dsc * xi) / dxnorm);
-    QB_WAVE_SYNC();
-    if (lane == 0) qb_trsv_t(Rs, LW, n, Us);
-    QB_WAVE_SYNC();
-    const double wl = lane < n ? Us[lane] : 0.0;
-    const double s2 = qb_wave_sum(wl * wl);
-    QB_WAVE_SYNC();                           // (Rs and Us are read no more)
-    return sqrt(s2);
-}
+// The state, the search bodies (bt_wave_core, bt_wg_core) and their helpers live in qr_batched_trust_dev.h, which qr_batched_lm.hip
+// includes as well; the kernels below read the radius and the starting guess and write the outputs.
 
 template <int W>
 __device__ __forceinline__ void bt_wave_search(const double (&r)[W], const qrd_bt_args& a, size_t q, int lane, const bd_lane& L, double* Rs,
                                                double* Xs)
 {
-    constexpr int LW = W + 1;
     const qrd_bd_args& d = a.d;
     const int n = d.n;
     const double delta = a.delta[q * a.sdelta], rtol = a.rtol;
@@ -121,56 +39,12 @@ __device__ __forceinline__ void bt_wave_search(const double (&r)[W], const qrd_b
         return;
     }
     const double lam0 = a.lam0 ? a.lam0[q * a.slam0] : 0.0;
-    double zl = 0.0, diag = 1.0;              // lane i: z_i and R(i, i)
-#pragma unroll
-    for (int c = 0; c < W; ++c) {
-        zl = c == n ? r[c] : zl;
-        if (c < n && lane == c) diag = r[c];
-    }
-    const int inf0 = qb_info_wave(diag, n, lane);
-    const int nsing = inf0 ? inf0 - 1 : n;
-    // the Gauss-Newton step: the leading nsing x nsing system, zeros below
-    double xi = bt_wave_solve<W>(r, n, nsing, lane, Rs, Xs);
-    double dxnorm = bt_wave_dxnorm(L.dsc, xi);
-    bt_state S;
-    S.fp = dxnorm - delta;
-    int it = 0, status = 1;
-    double lam = 0.0;
-    if (!(S.fp <= rtol * delta)) {
-        const double wnorm = nsing == n ? bt_wave_wnorm<W>(n, lane, L.dsc, xi, dxnorm, Rs, Xs + LW) : 0.0;
-        double gl = 0.0;                      // lane j: (sum over i <= j of R(i, j) z_i) / d_j
-#pragma unroll
-        for (int c = 0; c < W; ++c) {
-            if (c < n) {
-                const double t = qb_wave_sum(r[c] * zl);
-                if (lane == c) gl = t;
-            }
-        }
-        gl = (lane < n && L.dsc != 0.0) ? gl / L.dsc : 0.0;
-        const double gnorm = sqrt(qb_wave_sum(gl * gl));
-        bt_start(S, nsing == n, wnorm, gnorm, dxnorm, delta, lam0);
-        for (it = 1;; ++it) {
-            if (S.par == 0.0) S.par = fmax(DBL_MIN, 0.001 * S.paru);
-            lam = sqrt(S.par);
-            double w[W];
-            bd_wave_elim<W>(r, lam * L.dsc, n, n + 1, lane, w);
-            double dg = 1.0;
-#pragma unroll
-            for (int c = 0; c < W; ++c)
-                if (c < n && lane == c) dg = w[c];
-            const int inf = qb_info_wave(dg, n, lane);
-            if (inf) {                        // (wave-uniform: nothing else is written for this member)
-                if (lane == 0) d.info[q] = inf;
-                return;
-            }
-            xi = bt_wave_solve<W>(w, n, n, lane, Rs, Xs);
-            dxnorm = bt_wave_dxnorm(L.dsc, xi);
-            const double fpprev = S.fp;
-            S.fp = dxnorm - delta;
-            status = bt_leave(S, fpprev, delta, rtol, it, a.maxit);
-            if (status >= 0) break;           // (butterfly results: the same decision in every lane)
-            bt_update(S, bt_wave_wnorm<W>(n, lane, L.dsc, xi, dxnorm, Rs, Xs + LW), delta);
-        }
+    double zl;
+    bt_found F;
+    const double xi = bt_wave_core<W>(r, n, lane, L.dsc, delta, lam0 * lam0, rtol, a.maxit, Rs, Xs, zl, F);
+    if (F.info) {                             // (wave-uniform: nothing else is written for this member)
+        if (lane == 0) d.info[q] = F.info;
+        return;
     }
     // the outputs, as bd_wave_lams writes them for one lambda and one right-hand side
     double* xc = d.X + q * d.sX;
@@ -188,15 +62,12 @@ __device__ __forceinline__ void bt_wave_search(const double (&r)[W], const qrd_b
     }
     if (lane == 0) {
         d.info[q] = 0;
-        a.lam[q] = lam;
-        if (d.xnorm) d.xnorm[q] = dxnorm;
-        if (a.iter) a.iter[q] = it;
-        if (a.status) a.status[q] = status;
+        a.lam[q] = F.lam;
+        if (d.xnorm) d.xnorm[q] = F.dxnorm;
+        if (a.iter) a.iter[q] = F.it;
+        if (a.status) a.status[q] = F.status;
     }
 }
-
-template <int W>
-static constexpr size_t bt_wave_lds() { return sizeof(double) * 4 * 2 * W * (W + 1); }
 
 template <int W>
 __global__ void __launch_bounds__(256) bt_wave_kernel(const qrd_bt_args a)
@@ -231,32 +102,6 @@ __global__ void __launch_bounds__(256) bt_fused_wave_kernel(double* __restrict__
     bt_wave_search<W>(r, a, q, lane, L, Rs, Rs + W * LW);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// workgroup route: the images and words of bd_wg_lds with one right-hand side.  x lives in column n of the working copy, the vector of
-// the forward substitution (and g before the loop) in column n of the block, which the elimination leaves unused.
-// ---------------------------------------------------------------------------------------------------------------------------------
-
-// every thread: |D x| from the same LDS words, as bd_wg_kernel forms it
-__device__ __forceinline__ double bt_wg_dxnorm(const double* dsc, const double* xs, int n, int lane)
-{
-    const double xi = lane < n ? xs[lane] : 0.0;
-    const double dx = lane < n ? dsc[lane] * xi : 0.0;
-    return sqrt(bd_wave_dot(dx, dx));
-}
-
-// every thread: |w|, R^T w = D (D x / |D x|) over the image T; two barriers inside, one in front
-__device__ __forceinline__ double bt_wg_wnorm(const double* T, int ld, int n, const double* dsc, const double* xs, double dxnorm, double* us, int t)
-{
-    const int lane = t & 63;
-    __syncthreads();                          // (us is read no more)
-    if (t < n) us[t] = dsc[t] * ((dsc[t] * xs[t]) / dxnorm);
-    __syncthreads();
-    if (t == 0) qb_trsv_t(T, ld, n, us);
-    __syncthreads();
-    const double wl = lane < n ? us[lane] : 0.0;
-    return sqrt(qb_wave_sum(wl * wl));
-}
-
 __global__ void __launch_bounds__(256) bt_wg_kernel(const qrd_bt_args a)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -271,10 +116,8 @@ __global__ void __launch_bounds__(256) bt_wg_kernel(const qrd_bt_args a)
     double* rssv = dsc + 64;
     int* perm = (int*) (rssv + 64);
     int* sinfo = perm + 64;                   // sinfo[0]: info of an elimination, sinfo[1]: nsing
-    double* sdec = rssv + 1;                  // the decisions, published by thread 0 (one right-hand side: only rssv[0] is taken):
-                                              // [0] the Gauss-Newton step is accepted, [1] lambda of the coming elimination, [2] status
-    double* xs = Ws + (size_t) n * ld;
-    double* us = Ss + (size_t) n * ld;
+    double* sdec = rssv + 1;                  // the decisions, published by thread 0 (one right-hand side: only rssv[0] is taken)
+    const double* xs = Ws + (size_t) n * ld;
     const double delta = a.delta[q * a.sdelta], rtol = a.rtol;
     if (!bt_delta_ok(delta)) {                // (the same word in every thread)
         if (t == 0) d.info[q] = -1;
@@ -282,67 +125,11 @@ __global__ void __launch_bounds__(256) bt_wg_kernel(const qrd_bt_args a)
     }
     const double lam0 = a.lam0 ? a.lam0[q * a.slam0] : 0.0;
     bd_wg_load(d, q, t, Ms, ld, dsc, rssv, perm);
-    // the Gauss-Newton step: the leading nsing x nsing system of a copy of the master, zeros below
-    for (int idx = t; idx < ntot * n; idx += 256) {
-        const int c = idx / n, i = idx - c * n;
-        Ws[c * ld + i] = Ms[c * ld + i];
-    }
-    __syncthreads();
-    if (t == 0) {
-        const int inf0 = qb_info_serial(Ws, ld, n);
-        const int ns = inf0 ? inf0 - 1 : n;
-        sinfo[1] = ns;
-        for (int i = ns; i < n; ++i) xs[i] = 0.0;
-        qb_trsv(Ws, ld, ns, xs);
-    }
-    __syncthreads();
-    const int nsing = sinfo[1];
-    double dxnorm = bt_wg_dxnorm(dsc, xs, n, lane);
-    bt_state S;
-    S.fp = dxnorm - delta;
-    int it = 0, status = 1;
-    double lam = 0.0;
-    // Every wave forms the norms below from the same LDS words, but the search runs on thread 0's copy alone: it publishes each
-    // decision, and all 256 threads read that word after a barrier.  (With every wave deciding for itself, one member of the tests
-    // came back with X one unit in the last place off the damped solve of the lambda returned, from the row down whose diagonal entry
-    // of the block another wave had written: the block must hold one lambda, so one thread chooses it.)
-    if (t == 0) sdec[0] = S.fp <= rtol * delta ? 1.0 : 0.0;
-    __syncthreads();
-    if (sdec[0] == 0.0) {
-        const double wnorm = nsing == n ? bt_wg_wnorm(Ws, ld, n, dsc, xs, dxnorm, us, t) : 0.0;
-        __syncthreads();                      // (us is read no more)
-        for (int j = wv; j < n; j += 4) {     // wave wv: g_j = (sum over i <= j of R(i, j) z_i) / d_j for j = wv, wv + 4, ..
-            const double p = lane <= j ? Ms[j * ld + lane] * Ms[n * ld + lane] : 0.0;
-            const double g = qb_wave_sum(p);
-            if (lane == 0) us[j] = dsc[j] != 0.0 ? g / dsc[j] : 0.0;
-        }
-        __syncthreads();
-        const double gl = lane < n ? us[lane] : 0.0;
-        const double gnorm = sqrt(qb_wave_sum(gl * gl));
-        bt_start(S, nsing == n, wnorm, gnorm, dxnorm, delta, lam0);
-        for (it = 1;; ++it) {
-            if (S.par == 0.0) S.par = fmax(DBL_MIN, 0.001 * S.paru);
-            if (t == 0) sdec[1] = sqrt(S.par);
-            __syncthreads();
-            lam = sdec[1];
-            bd_wg_elim(Ms, Ws, Ss, dsc, lam, n, ntot, ld, t);
-            if (t == 0) sinfo[0] = qb_info_serial(Ws, ld, n);
-            __syncthreads();
-            if (sinfo[0]) {                   // (the same word in every thread: nothing else is written for this member)
-                if (t == 0) d.info[q] = sinfo[0];
-                return;
-            }
-            if (t == 0) qb_trsv(Ws, ld, n, xs);
-            __syncthreads();
-            dxnorm = bt_wg_dxnorm(dsc, xs, n, lane);
-            const double fpprev = S.fp;
-            S.fp = dxnorm - delta;
-            if (t == 0) sdec[2] = (double) bt_leave(S, fpprev, delta, rtol, it, a.maxit);
-            __syncthreads();
-            status = (int) sdec[2];
-            if (status >= 0) break;           // (the same word in every thread)
-            bt_update(S, bt_wg_wnorm(Ws, ld, n, dsc, xs, dxnorm, us, t), delta);
-        }
+    bt_found F;
+    bt_wg_core(Ms, Ws, Ss, dsc, sdec, sinfo, n, ld, delta, lam0 * lam0, rtol, a.maxit, t, F);
+    if (F.info) {                             // (the same word in every thread: nothing else is written for this member)
+        if (t == 0) d.info[q] = F.info;
+        return;
     }
     if (wv == 0) {                            // the outputs, as bd_wg_kernel writes them for one lambda and one right-hand side
         double* xc = d.X + q * d.sX;
@@ -360,10 +147,10 @@ __global__ void __launch_bounds__(256) bt_wg_kernel(const qrd_bt_args a)
         }
         if (lane == 0) {
             d.info[q] = 0;
-            a.lam[q] = lam;
-            if (d.xnorm) d.xnorm[q] = dxnorm;
-            if (a.iter) a.iter[q] = it;
-            if (a.status) a.status[q] = status;
+            a.lam[q] = F.lam;
+            if (d.xnorm) d.xnorm[q] = F.dxnorm;
+            if (a.iter) a.iter[q] = F.it;
+            if (a.status) a.status[q] = F.status;
         }
     }
 }

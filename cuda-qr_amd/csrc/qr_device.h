@@ -436,6 +436,35 @@ typedef struct qrd_bt_args {
 int qrd_bt_solve(void* stream, const qrd_bt_args* a);
 int qrd_bt_fused(void* stream, double* A, int m, int lda, size_t strideA, double* tau, size_t stridetau, double* B, const qrd_bt_args* a);
 
+/* batched Levenberg-Marquardt (qr_batched_lm.hip, called from qr_batched_lm.c only; mi355x_qr.h section 8m): MINPACK lmder's outer loop
+ * per member in two launches per round.
+ *   qrd_blm_state: the packed per-member arrays of a solver (x, xtrial, D: n each; the others one each); the fields and their order are
+ *   those of the public qr_lm_batched_state.  qrd_blm_opts: the fields of qr_lm_options.
+ *   qrd_blm_start: x <- X0 (n per member, sX apart), D <- D0 (mode 2; sD apart, 0: shared) or ones, iter = nfev = 1, everything else 0.
+ *   qrd_blm_step: d carries the factors as qrd_bd_args does (R, Z, rss, jpvt, their strides, n, zrows, batch; nrhs = nlam = 1; D, lam, X,
+ *   xnorm, resid, info and flip unset).  Per member with status == 0 and info == 0: fnorm, acnorm, the first step's D, xnorm and delta,
+ *   gnorm and the gtol test, the search of qrd_bt_solve (the same device code) on D, delta and par, xtrial, prered, dirder, njev.  One
+ *   launch: a wave per member for n + 1 <= 32, else a workgroup per member (n <= 63).
+ *   qrd_blm_update: Ft (m rows per member, sF apart) is f at xtrial: the gain ratio, delta, par, accept or reject, nfev, the stopping
+ *   tests.  One launch, a wave per member.  batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_blm_state {
+    double *x, *xtrial, *D, *delta, *par, *fnorm, *xnorm, *pnorm, *gnorm, *prered, *dirder;
+    int *iter, *nfev, *njev, *accepted, *status, *info, *par_status;
+} qrd_blm_state;
+typedef struct qrd_blm_opts {
+    double ftol, xtol, gtol, factor, par_rtol;
+    int maxfev, mode, par_maxit;
+} qrd_blm_opts;
+typedef struct qrd_blm_step_args {
+    qrd_bd_args d;
+    qrd_blm_state s;
+    qrd_blm_opts o;
+} qrd_blm_step_args;
+int qrd_blm_start(void* stream, const double* X0, int ldx, size_t sX, const double* D0, size_t sD, int n, int batch, const qrd_blm_state* s,
+                  int mode);
+int qrd_blm_step(void* stream, const qrd_blm_step_args* a);
+int qrd_blm_update(void* stream, const double* Ft, int m, int ldf, size_t sF, int n, int batch, const qrd_blm_state* s, const qrd_blm_opts* o);
+
 /* batched equality-constrained least squares (qr_batched_lse.hip, called from qr_batched_lse.c only; mi355x_qr.h section 8h).  Per member
  * min |A x - b| subject to C x = d by the null-space method: C^T = Q_c [R_c ; 0], R_c^T y1 = d, A~ = A Q_c, the QR of A~(:, p:n) with
  * A~(:, 0:p) and b - A~(:, 0:p) y1 riding along, R_a y2 = the top of it, x = Q_c [y1 ; y2], resid from the tail, R_c lambda = g.

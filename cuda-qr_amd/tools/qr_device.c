@@ -81,6 +81,12 @@
  * through one qr_gels_stats_batched_dev call with every output (QR_COV_UNSCALED, no weights).  Printed: the time, the worst |sum h - n|,
  * the worst ||C A^T A - I||_F (formed on the host), and the number of non-zero info words.
  *
+ * `./qr_device m 3 --batched count --lm` does nothing else either: `count` seeded exponential-decay fits y = a exp(-b t) + c on m points of
+ * [0, 4] (planted (a, b, c), zero residual, the start the planted values times 1.2 or 0.8) go through qr_lstsq_lm_batched, the host twin of
+ * the batched Levenberg-Marquardt solver: the model runs on the host between the device calls, so the time is dominated by it and by the
+ * copies.  Printed: the time, the worst ||x - planted||, the mean and the largest nfev, the number of non-zero info words and a histogram
+ * of status.
+ *
  * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
  * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
  * qr_lsacc_batched_slide_dev for the whole batch -- beside one qr_gels_batched_dev per window on copies of the windows: both wall times
@@ -1013,6 +1019,82 @@ static int batched_trust_main(int m, int n, int count, double frac)
     return 0;
 }
 
+/* the model of --lm on host buffers: y = a exp(-b t) + c on m points of [0, 4] */
+typedef struct lm_model {
+    int m;
+    const double* y;              /* count x m: the planted curves */
+} lm_model;
+
+static int lm_expdecay(void* user, int what, const double* X, int batch, double* F, double* J)
+{
+    const lm_model* M = (const lm_model*) user;
+    const int m = M->m;
+    for (int q = 0; q < batch; q++) {
+        const double a = X[3 * (size_t) q], b = X[3 * (size_t) q + 1], c = X[3 * (size_t) q + 2];
+        for (int i = 0; i < m; i++) {
+            const double t = m > 1 ? 4.0 * i / (m - 1) : 0.0, e = exp(-b * t);
+            if (what == 2) {
+                double* Jq = J + (size_t) q * m * 3;
+                Jq[i] = e; Jq[m + i] = -a * t * e; Jq[2 * m + i] = 1.0;
+            } else {
+                F[(size_t) q * m + i] = a * e + c - M->y[(size_t) q * m + i];
+            }
+        }
+    }
+    return 0;
+}
+
+/* count exponential-decay fits of m points (n = 3) through the host twin of the batched Levenberg-Marquardt solver */
+static int batched_lm_main(int m, int n, int count)
+{
+    if (n != 3 || m < 3 || m > qr_batched_max_rows(4) || count < 1) {
+        fprintf(stderr, "--batched count --lm fits a exp(-b t) + c: needs n == 3, 3 <= m <= %d and count >= 1\n", qr_batched_max_rows(4));
+        return 1;
+    }
+    printf("Exact problem size: %d exponential-decay fits of %d points, start = planted x (1 +- 0.2)\n", count, m);
+    const size_t nc = (size_t) count;
+    double *xs = malloc(sizeof(double) * 3 * nc), *X = malloc(sizeof(double) * 3 * nc), *y = malloc(sizeof(double) * nc * (size_t) m);
+    double* fnorm = malloc(sizeof(double) * nc);
+    int *nfev = malloc(sizeof(int) * nc), *njev = malloc(sizeof(int) * nc), *status = malloc(sizeof(int) * nc), *info = malloc(sizeof(int) * nc);
+    if (!xs || !X || !y || !fnorm || !nfev || !njev || !status || !info) { fprintf(stderr, "out of memory\n"); return 1; }
+    srand(12);
+    for (size_t q = 0; q < nc; q++) {
+        xs[3 * q] = 1.0 + (double) rand() / RAND_MAX;
+        xs[3 * q + 1] = 0.5 + (double) rand() / RAND_MAX;
+        xs[3 * q + 2] = 0.25 + 0.5 * rand() / RAND_MAX;
+        for (int i = 0; i < m; i++) y[q * m + i] = xs[3 * q] * exp(-xs[3 * q + 1] * (m > 1 ? 4.0 * i / (m - 1) : 0.0)) + xs[3 * q + 2];
+    }
+    lm_model M = {m, y};
+    double el = 0.0;
+    for (int t = -1; t < TRIALS; t++) {
+        srand(13);
+        for (size_t i = 0; i < 3 * nc; i++) X[i] = xs[i] * (rand() & 1 ? 1.2 : 0.8);
+        const double t0 = now();
+        const int rc = qr_lstsq_lm_batched(lm_expdecay, &M, m, 3, count, X, NULL, NULL, fnorm, nfev, njev, status, info);
+        if (rc && rc != QR_E_SINGULAR) { fprintf(stderr, "qr_lstsq_lm_batched failed: %s\n", qr_strerror(rc)); return 1; }
+        if (t >= 0) el += now() - t0;
+    }
+    int hist[10] = {0}, most = 0, failed = 0;
+    double worst = 0.0, mean = 0.0;
+    for (size_t q = 0; q < nc; q++) {
+        if (info[q]) failed++;
+        hist[status[q] >= 0 && status[q] <= 8 ? status[q] : 9]++;
+        mean += nfev[q];
+        if (nfev[q] > most) most = nfev[q];
+        double e = 0.0;
+        for (int j = 0; j < 3; j++) e += (X[3 * q + j] - xs[3 * q + j]) * (X[3 * q + j] - xs[3 * q + j]);
+        if (sqrt(e) > worst) worst = sqrt(e);
+    }
+    printf(" MMQR ran %d Levenberg-Marquardt fits of %d points in %f s (avg over %d)   [host twin: the model runs on the host between the "
+           "device calls]\n", count, m, el / TRIALS, TRIALS);
+    printf(" worst |x - planted| = %.2e   nfev mean %.2f max %d   info != 0: %d\n status:", worst, mean / count, most, failed);
+    for (int s = 0; s < 10; s++)
+        if (hist[s]) printf(s < 9 ? "  %d: %d" : "  other: %d", s < 9 ? s : hist[s], hist[s]);
+    printf("\n");
+    free(xs); free(X); free(y); free(fnorm); free(nfev); free(njev); free(status); free(info);
+    return 0;
+}
+
 /* count problems min |A x - b| subject to C x = d (A m x n, C p x n) through one qr_gglse_batched_dev call */
 static int batched_lse_main(int m, int n, int count, int p)
 {
@@ -1521,7 +1603,7 @@ static int batched_stats_main(int m, int n, int count)
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --lsei mg [neq] | --robust frac | --stats]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --lsei mg [neq] | --robust frac | --stats | --lm]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -1559,6 +1641,8 @@ int main(int argc, char** argv)
                 if (strcmp(argv[k], "--lsei") == 0)
                     return batched_lsei_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atoi(argv[k + 1]) : 1,
                                              k + 2 < argc ? atoi(argv[k + 2]) : 0);
+            for (int k = 3; k < argc; k++)
+                if (strcmp(argv[k], "--lm") == 0) return batched_lm_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--bvls") == 0) return batched_bvls_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)

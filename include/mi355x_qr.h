@@ -1074,7 +1074,9 @@ int qr_lstsq_damped_batched(const double* A, int m, int n, const double* B, int 
  * three LDS images, thread 0 publishing every decision in an LDS word that all threads read after a barrier.  Both compile to no
  * scratch memory.
  *
- * Out of scope: the outer Levenberg-Marquardt loop (the Jacobian, the gain ratio, the update of Delta); several right-hand sides per
+ * The outer Levenberg-Marquardt loop (the gain ratio, the update of Delta) is section 8m, which runs this search's device code.
+ *
+ * Out of scope: several right-hand sides per
  * member; a general D for wide members; a fused launch on the workgroup route; blocked / MFMA variants of the elimination.
  * ------------------------------------------------------------------------------------------- */
 
@@ -1546,6 +1548,113 @@ int qr_lsei_batched_dev(qr_plan* plan,
 int qr_lstsq_inequality_batched(const double* A, int m, int n, const double* b, const double* G, int mg, int neq, const double* h,
                                 int maxit, double rcond, int batch,
                                 double* X, double* MU, double* S, int* state, double* resid, int* iter, int* info);
+
+/* ---------------------------------------------------------------------------------------------
+ * 8m. Batched Levenberg-Marquardt: MINPACK lmder's outer loop for every member of a batch,
+ *
+ *         min |f(x)|_2,      f: R^n -> R^m, m >= n, 1 <= n <= QR_BATCHED_MAX_N - 1, m <= qr_batched_max_rows(n + 1),
+ *
+ * with the Jacobian J(x) (m x n) supplied by the caller -- per-pixel curve fitting, damped inverse kinematics with a step limit, the users
+ * sections 8f, 8g and 8k were built for (qrsolv, lmpar and covar; this is lmder around them).  The loop is split by reverse
+ * communication into two device calls, so that the caller's model code runs between them on the same stream and no call but
+ * qr_lm_batched_running waits on the host:
+ *
+ *     qr_lm_batched_start_dev(lm, dX0, ...);
+ *     repeat:  fill J(x) and f(x) of every member at state.x;   qr_lm_batched_step_dev(lm, dJ, ..., dF, ...);
+ *              fill f(xtrial) of every member at state.xtrial;  qr_lm_batched_update_dev(lm, dFtrial, ...);
+ *              every few rounds: qr_lm_batched_running(lm, &count), until count == 0
+ *
+ * A member that the update rejected keeps its x, so the caller hands in the same J and f again and the factorisation returns the same
+ * bits: one rule for every member, no branch on the host.  A member whose status or info word is not 0 is skipped by both kernels: what
+ * the caller leaves in its slots of J and F is factored but never used, its state stays bitwise frozen, and its neighbours are
+ * unaffected.  step twice in a row, update before a step and either before start return QR_E_ARG from a phase flag kept on the host.
+ *
+ * Layout: section 8's (member q at base + q * stride, column-major, strides in elements); the stride rules are section 8g's.  The plan
+ * supplies the stream only.  QR_E_ARG for bad arguments before anything touches a device; batch == 0 is allowed (nothing is launched).
+ *
+ * The state (qr_lm_batched_view; packed per-member device arrays, read-only for the caller): x, xtrial, D (n each); delta, par (MINPACK's
+ * par = lambda^2, not lambda), fnorm, xnorm = |D x|, pnorm = |D p|, gnorm, prered, dirder; iter, nfev, njev (the steps run), accepted
+ * (0 / 1: what the last update did), status, info, par_status (section 8g's status of the last search).
+ *   status: 0 running; MINPACK's info otherwise: 1 ftol, 2 xtol, 3 both, 4 gnorm <= gtol, 5 nfev >= maxfev, 6 ftol too small,
+ *           7 xtol too small, 8 gtol too small; -1: the member has an info word from the search.
+ *   info:   0; -1 for a D of mode 2 with an entry that is not > 0 (found by the first step: nothing else is written, status stays 0, and
+ *           the member is skipped from then on) or for a radius that is no finite positive number; i + 1 for the smallest i with a zero
+ *           on the diagonal of a damped triangle (section 8g's words; status is then -1).
+ *
+ * qr_lm_batched_step_dev: qr_geqp3_batched_dev's launch on dJ, qr_ormqr_batched_dev's 'T' launch on dF, then one new launch: dJ returns as
+ * geqp3 leaves it and dF as Q^T f.  qr_lm_step_batched_dev is that one new launch alone for factors the caller already has (R, the top
+ * zrows >= n rows of Q^T f, the sum of squares of the rows that are not there in drss, jpvt or NULL: section 8g's operand rules); the R
+ * and Z of a batched accumulator qualify.  Per running member, with MINPACK's names:
+ *   a. fnorm = sqrt(sum over all rows of (Q^T f)^2 (+ drss)), recomputed at every step by this one rule.  MINPACK takes |f| from f itself:
+ *      the two are equal to rounding.
+ *   b. acnorm[jpvt[k]] = |R(0:k, k)|, the norm of the column of J through its column of R.  MINPACK takes it from J before factoring: the
+ *      two are equal to rounding.
+ *   c. the member's first step: mode 1: D_j = acnorm_j, or 1 where that is 0; mode 2: D is qr_lm_batched_start_dev's; xnorm = |D x|;
+ *      delta = factor * xnorm, or factor if that is 0.
+ *   d. gnorm = max over k with acnorm != 0 of |sum_{i<=k} R(i,k) (z_i / fnorm)| / acnorm[jpvt[k]], 0 if fnorm == 0; gnorm <= gtol: status 4.
+ *   e. mode 1: D = max(D, acnorm).
+ *   f. section 8g's search (the same device code: p, par, pnorm and par_status are bitwise qr_trust_batched_dev's on the same factors, D,
+ *      delta and start) from par, with par_rtol and par_maxit.
+ *   g. xtrial = x - p; while iter == 1 (no step accepted yet): delta = min(delta, pnorm).
+ *   h. temp1 = |R P^T p| / fnorm (each row's sum over the columns ascending), temp2 = sqrt(par) pnorm / fnorm.
+ *   i. prered = temp1^2 + temp2^2 / 0.5, dirder = -(temp1^2 + temp2^2), njev += 1.
+ * qr_lm_batched_update_dev, per running member: fnorm1 = |ftrial|; actred = 1 - (fnorm1 / fnorm)^2 if 0.1 fnorm1 < fnorm, else -1 (a
+ * fnorm1 that is NaN or inf counts as -1: an addition to MINPACK, such a trial point is rejected and delta shrinks); ratio = actred /
+ * prered (0 if prered == 0); lmder's rules for delta and par (the ratio <= 0.25 branch with temp, its 0.1 floor, delta = temp min(delta,
+ * pnorm / 0.1), par /= temp; the par == 0 or ratio >= 0.75 branch); acceptance at ratio >= 1e-4 (x = xtrial, xnorm = |D x|, fnorm =
+ * fnorm1, iter += 1); nfev += 1; the stopping tests in MINPACK's order (1, 2, 3, then 5, 6, 7, 8).
+ *
+ * Routes, by shape alone: the step is a wave per member (four per workgroup, no barrier) for n + 1 <= 32, else a workgroup per member;
+ * the update is a wave per member.  No atomics, every sum in a fixed order: a member's results do not depend on the batch size or on its
+ * place in the batch, and repeats are bitwise equal.
+ *
+ * Out of scope: a fused factor-and-step launch on the wave route; lmdif's finite-difference Jacobian; bounds or constraints on x;
+ * m < n; skipping the refactorisation of rejected members; several residual vectors per member.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct qr_lm_batched qr_lm_batched;
+
+typedef struct {
+    double ftol, xtol, gtol, factor, par_rtol;
+    int maxfev, mode, par_maxit;
+} qr_lm_options;
+
+typedef struct {
+    double *x, *xtrial, *D, *delta, *par, *fnorm, *xnorm, *pnorm, *gnorm, *prered, *dirder;
+    int *iter, *nfev, *njev, *accepted, *status, *info, *par_status;
+} qr_lm_batched_state;
+
+/* the host-pointer twin's model: what = 1: F (batch x m, member after member) <- f at X (batch x n); 2: J (batch matrices m x n,
+ * column-major) <- the Jacobian at X; 3: F <- f at X, X being the trial points.  A non-zero return stops the solve and is returned. */
+typedef int (*qr_lm_fcn)(void* user, int what, const double* X, int batch, double* F, double* J);
+
+/* MINPACK lmder1's: ftol = xtol = sqrt(DBL_EPSILON), gtol = 0, factor = 100, mode = 1, par_rtol = 0.1, par_maxit = 10; maxfev = 0 stands
+ * for 100 (n + 1) */
+void qr_lm_options_default(qr_lm_options* opt);
+
+/* opt NULL: the defaults.  QR_E_ARG for ftol, xtol or gtol < 0, factor <= 0, mode not 1 or 2, par_rtol outside (0, 1), par_maxit < 1,
+ * maxfev < 0 (NaN anywhere included) and for a shape outside the rules above. */
+int qr_lm_batched_create(qr_lm_batched** lm, qr_plan* plan, int m, int n, int batch, const qr_lm_options* opt);
+/* dX0: n per member (ldx >= n, strideX >= ldx); dD0: the scaling of mode 2, n per member (strideD 0: shared, else >= n), not read in mode 1 */
+int qr_lm_batched_start_dev(qr_lm_batched* lm, const double* dX0, int ldx, long long strideX, const double* dD0, long long strideD);
+/* dJ: m x n (ldj >= m, strideJ >= ldj * n), dF: m per member (ldf >= m, strideF >= ldf) */
+int qr_lm_batched_step_dev(qr_lm_batched* lm, double* dJ, int ldj, long long strideJ, double* dF, int ldf, long long strideF);
+int qr_lm_batched_update_dev(qr_lm_batched* lm, const double* dFtrial, int ldf, long long strideF);
+int qr_lm_batched_view(qr_lm_batched* lm, qr_lm_batched_state* state);
+/* count <- the members with status == 0 and info == 0.  The one call that waits on the host. */
+int qr_lm_batched_running(qr_lm_batched* lm, int* count);
+int qr_lm_batched_destroy(qr_lm_batched* lm);
+
+/* The step from factors that exist, in qr_lm_batched_step_dev's place in the protocol: dR n x n (ldr >= n, strideR >= ldr * n; the upper
+ * triangle is read), dZ zrows x 1 (n <= zrows <= ldz <= strideZ), drss (one per member, may be NULL: 0), djpvt (n per member,
+ * stridejpvt >= n; NULL: the identity). */
+int qr_lm_step_batched_dev(qr_lm_batched* lm, const double* dR, int ldr, long long strideR, const double* dZ, int zrows, int ldz,
+                           long long strideZ, const double* drss, const int* djpvt, long long stridejpvt);
+
+/* The whole solve of a packed batch on host pointers: X (batch x n) holds the starts on entry and the results on return; D: the scaling
+ * of mode 2 (batch x n), else NULL; fnorm, nfev, njev, status (may be NULL) and info: one per member.  fcn is called on host buffers.
+ * Returns QR_E_SINGULAR if any info word is non-zero.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_lm_batched(qr_lm_fcn fcn, void* user, int m, int n, int batch, double* X, const double* D, const qr_lm_options* opt,
+                        double* fnorm, int* nfev, int* njev, int* status, int* info);
 
 #ifdef __cplusplus
 }
