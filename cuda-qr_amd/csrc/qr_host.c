@@ -440,6 +440,7 @@ static int plan_create_impl(qr_plan** out, int m, int n, int nb, int ib, int tsq
     for (int e = 0; e < 2 && !rc; ++e) {
         rc = qrd_event_create_notiming(&p->ev_panel[e]);
         if (!rc) rc = qrd_event_create_notiming(&p->ev_wide[e]);
+        if (!rc) rc = qrd_event_create_notiming(&p->ev_tree[e]);
     }
     size_t cap = (size_t) 256 * nb * (size_t) n;
     if (cap > ((size_t) 16 << 20)) cap = (size_t) 16 << 20;
@@ -508,6 +509,7 @@ int qr_plan_destroy(qr_plan* p)
         if (p->ev_panel[e]) qrd_event_destroy(p->ev_panel[e]);
         if (p->ev_v[e]) qrd_event_destroy(p->ev_v[e]);
         if (p->ev_wide[e]) qrd_event_destroy(p->ev_wide[e]);
+        if (p->ev_tree[e]) qrd_event_destroy(p->ev_tree[e]);
         qrd_free(p->Vw2[e]); qrd_free(p->VT2[e]); qrd_free(p->T2[e]);
     }
     qrd_free(p->Wn); qrd_free(p->slabs_u); qrd_free(p->We); qrd_free(p->Ye); qrd_free(p->Yn); qrd_free(p->Ye2);
@@ -1333,7 +1335,9 @@ static int geqrf_issue_inner(qr_plan* p, double* dA, int m, int n, int lda, doub
      *   N(s)  needs P(s) (stream order / ev_panel) and W(s-1) (ev_wide[(s-1)&1] / stream order);
      *   W(s)  needs P(s) (ev_panel[s&1]) and W(s-1) (stream order);
      *   P(s+1)'s second half needs W_a(s) (ev_half[s&1]);
-     *   P(s+2) overwrites panel set s&1, which W(s) reads: ordered through N(s+1)'s wait on ev_wide[s&1]. */
+     *   P(s+2) overwrites panel set s&1, which W(s) reads: ordered through N(s+1)'s wait on ev_wide[s&1];
+     *   P(s+1) needs the merge tree of panel s where that ran behind N(s) on the update stream (ev_tree[s&1]): G and X are the plan's
+     *   only ones, the tree reads and writes them, P(s+1) writes them. */
     int wide_pending[2] = {0, 0}, extra_pending = 0;
     int v_recorded[2] = {0, 0};     /* ev_v[e] was recorded inside factor_panel for the panel now in set e */
     int t_deferred[2] = {0, 0};     /* the panel now in set e left its T merge to this loop (deferred_t_merge) */
@@ -1410,7 +1414,13 @@ static int geqrf_issue_inner(qr_plan* p, double* dA, int m, int n, int lda, doub
             }
             CHECK(qrd_event_record(p->ev_next[e], p->stream_u));
             CHECK(qrd_stream_wait_event(p->stream, p->ev_next[e]));
-            if (!need_tree_first) CHECK(deferred_tree(p, p->stream_u, e, wout, dtau + k));      /* W(s), next on this stream, needs the merged T */
+            if (!need_tree_first) {
+                CHECK(deferred_tree(p, p->stream_u, e, wout, dtau + k));      /* W(s), next on this stream, needs the merged T */
+                /* P(s+1) needs this tree: it reads G and fills X here while P(s+1), released by ev_next above, writes its own Gram blocks
+                 * into the same G and merges through the same X on the panel stream */
+                CHECK(qrd_event_record(p->ev_tree[e], p->stream_u));
+                CHECK(qrd_stream_wait_event(p->stream, p->ev_tree[e]));
+            }
             wide_pending[e ^ 1] = 0;
         } else if (n_on_u) {
             /* N(s) on the update stream: behind W(s-1) by stream order, after P(s) (ev_panel) and E(s-1) (ev_extra) */

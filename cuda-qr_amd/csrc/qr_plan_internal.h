@@ -47,6 +47,7 @@ struct qr_plan {
                                  * T merge to the caller (deferred_t_merge, on the update stream: 224 compute units instead of the panel stream's 32);
                                  * t_deferred: factor_panel did so */
     void* ev_wide[2];           /* wide update that read panel set s finished */
+    void* ev_tree[2];           /* the merge tree of panel set s that ran BEHIND N(s) on the update stream has finished with G and X */
     double *Vw, *VT, *T;        /* current panel set (aliases of set[cur]) */
     double *Vw2[2], *VT2[2], *T2[2];
     int vt_formed[2];           /* VT2[e] = Vw2[e] * T2[e] of the panel NOW in set e exists (cleared when a panel is factored into the set,

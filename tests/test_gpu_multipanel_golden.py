@@ -100,6 +100,14 @@ np.save(sys.argv[1], O.sign_normalise(F))
     (256, {"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "64:0.5,U", "MI355XQR_BALANCE": "14,44,0,0"}),   # late phase: panel chain on an unmasked stream
     (256, {"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "32", "MI355XQR_BALANCE": "14,44,0,0", "MI355XQR_TN_WIDE": "1"}),   # wide-tile TN product
     (256, {"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "32", "MI355XQR_BALANCE": "14,44,0,0", "MI355XQR_KPIPE": "0", "MI355XQR_NT_IL": "0"}),   # plain K loops (round-2 issue order) in the update's two GEMMs
+    # schedule variants the stream-order check drives over the stub (tests/test_schedule_order.py; `host_order factor 2024 2024 nb` under the
+    # same environment shows the branch taken): at nb 128 on a 32-CU panel stream one panel per factorisation leaves its Gram matrix and T
+    # merge to the update stream ...
+    (128, {"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "32", "MI355XQR_BALANCE": "14,44,0,0", "MI355XQR_DEFER_T": "0"}),   # ... not here: merged on the panel stream
+    (128, {"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "32", "MI355XQR_BALANCE": "14,44,0,0", "MI355XQR_TRSM": "0"}),      # ... merge tree first, then N(s) with the merged T
+    (128, {"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "32", "MI355XQR_BALANCE": "14,44,0,0", "MI355XQR_SPLIT_T": "0"}),   # N(s) on the update stream waits for the whole panel (no ev_v)
+    (256, {"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "64:0.5,32"}),                                                        # two masked phases: both streams hop, the model follows the phase
+    (256, {"MI355XQR_LOOKAHEAD": "1", "MI355XQR_SPLIT": "64", "MI355XQR_NEXT": "panel"}),                                     # N(s) on the panel stream of a partition
 ])
 def test_2024_square_vs_reference_R_slices(qr, oracle, tmp_path, nb, env):
     """16 (nb = 128) / 8 / 32 outer panels: wide update, look-ahead, CU partition, balance_cols -- against slices of the

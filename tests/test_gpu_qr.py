@@ -510,6 +510,38 @@ def test_geqrf_is_deterministic(qr):
     p.close()
 
 
+def test_calls_queued_without_a_sync_equal_synced_calls(qr):
+    """geqrf, extract_r, applyq(identity) and a geqrf of a second matrix queued on one plan with a single sync at the end, against the same
+    calls with a sync after each: the workspaces (panel sets, G, X, W, slabs) of the second factorisation meet the first one's wide update
+    and the Q formation only through stream order and the schedule's events.  3920 x 2048 is the smallest shape (of whole 16-row tiles) at
+    which the default plan takes look-ahead on a CU partition (n >= 2048, m n >= 8e6).  One deterministic schedule: bitwise equality."""
+    m, n = 3920, 2048
+    p = qr.Plan(m, n)
+    assert p.info()[2] and 0 < p.update_cus() < 256          # look-ahead, and the wide update on its share of a partition
+
+    def run(sync_each):
+        dA, dB, dQ, dR, dR2 = zeros(m, n), zeros(m, n), zeros(m, n), zeros(n, n), zeros(n, n)
+        dtau, dtau2 = zeros(n, 1), zeros(n, 1)
+        p.fill_uniform(dA, m, m, n, seed=5)
+        p.fill_uniform(dB, m, m, n, seed=6)
+        p.sync()
+        for call in (lambda: p.geqrf(dA, m, n, m, dtau), lambda: p.extract_r(dA, m, n, m, dR, n, n),
+                     lambda: p.applyq(dA, m, n, m, dtau, dQ, n, m, True), lambda: p.geqrf(dB, m, n, m, dtau2),
+                     lambda: p.extract_r(dB, m, n, m, dR2, n, n)):
+            call()
+            if sync_each:
+                p.sync()
+        p.sync()
+        return host(dR), host(dQ), host(dR2)
+
+    ref = run(True)
+    got = run(False)
+    assert np.isfinite(ref[0]).all() and np.abs(np.diag(ref[0])).min() > 0 and not np.array_equal(ref[0], ref[2])
+    for name, a, b in zip(("R of the first matrix", "Q of the first matrix", "R of the second matrix"), got, ref):
+        assert np.array_equal(a, b), f"{name}: {np.count_nonzero(a != b)} entries differ, max |diff| {np.abs(a - b).max():.3e}"
+    p.close()
+
+
 def test_profile_hooks(qr):
     m, n = 2048, 1024
     p = qr.Plan(m, n)
