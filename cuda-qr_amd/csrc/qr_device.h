@@ -207,7 +207,7 @@ int qrd_device_info(char* name, int name_len, int* cus, int* clock_khz, size_t* 
 int qrd_probe_mfma_f64(double* out3);
 int qrd_probe_copy(double* gbps);
 
-/* least-squares solve (qr_solve.hip, called from qr_solve.c only -- the stub device layer of the sanitizer builds does not have them).
+/* least-squares solve (qr_solve.hip, called from qr_solve.c only).
  * qrd_ormqr_skinny: Cs (mk x nrhs, ldc) <- (I - V op(T) V^T) Cs for the panel whose V is the unit lower trapezoid of Ak (mk x w, lda;
  * read in place) and whose T is upper triangular (ldt); trans_t = 1: op(T) = T^T (Q^T C), 0: T (Q C).  ws: qrd_ormqr_skinny_ws doubles.
  * Three launches, fixed-order sums.  -7: shape not taken (w > QRD_SOLVE_MAX_W).
@@ -220,7 +220,7 @@ int qrd_ormqr_skinny(void* stream, const double* Ak, int lda, int mk, int w, con
                      int nrhs, double* ws);
 int qrd_trsm_step(void* stream, const double* R, int lda, double* B, int ldb, int nrhs, int row_lo, int l0, int l1, int x0, int x1);
 
-/* minimum-norm solve (qr_minnorm.hip, called from qr_minnorm.c only -- as above, the stub device layer does not have them).
+/* minimum-norm solve (qr_minnorm.hip, called from qr_minnorm.c only).
  * qrd_trsm_t_step: the mirror of qrd_trsm_step for R^T X = B: rows [l0, row_hi) of B -= R[x0:x1, rows]^T B[x0:x1], then
  * R[l0:l1, l0:l1]^T X = B[l0:l1] solved in place (l1 - l0 <= 64, x1 - x0 <= 64, x1 <= l0; x0 == x1: no update).
  * qrd_transpose_tiled: D (cols x rows, ldd) = S (rows x cols, lds)^T on 64 x 64 tiles through LDS, both sides contiguous; any sizes,
@@ -228,7 +228,7 @@ int qrd_trsm_step(void* stream, const double* R, int lda, double* B, int ldb, in
 int qrd_trsm_t_step(void* stream, const double* R, int lda, double* B, int ldb, int nrhs, int row_hi, int l0, int l1, int x0, int x1);
 int qrd_transpose_tiled(void* stream, int rows, int cols, const double* S, int lds, double* D, int ldd);
 
-/* row-append update (qr_update.hip, called from qr_update.c only -- as above, the stub device layer does not have them).
+/* row-append update (qr_update.hip, called from qr_update.c only).
  * qrd_tp_panel: [Rkk (w x w upper triangle, ldr; its strict lower triangle is neither read nor written) ; Bk (p x w, ldb)] factored in
  * place by one workgroup: R' over the triangle, V over Bk, the w x w T (zeros below its diagonal) to Tk (ldt); w <= QRD_TP_W, p <= QRD_TP_MAXROWS.
  * qrd_tp_apply: W = op(Tk) (C1k + Vk^T C2), C1k -= W, C2 -= Vk W over ncols columns (C1k: w rows; C2: p rows), one workgroup per 32
@@ -242,7 +242,7 @@ int qrd_tp_apply(void* stream, int trans_t, const double* Vk, int ldv, int p, in
 int qrd_tp_colssq_add(void* stream, const double* X, int ldx, int rows, int cols, double* acc);
 int qrd_tp_sqrt(void* stream, const double* in, double* out, int n);
 
-/* signed-row update (qr_downdate.hip, called from qr_downdate.c only -- as above, the stub device layer does not have them): the rows
+/* signed-row update (qr_downdate.hip, called from qr_downdate.c only): the rows
  * [0, p_add) of a block count +1, the rows [p_add, p) count -1 (S = diag of those signs).  status: one device int, 0 while all is well;
  * every launch reads it first and returns at once when it is not 0.
  * qrd_th_panel: qrd_tp_panel with every inner product over the p rows weighted by S; a column whose d = R(j,j)^2 + b^T S b is <= 0 or
@@ -254,7 +254,7 @@ int qrd_th_apply(void* stream, const double* Vk, int ldv, int p, int p_add, int 
                  double* C2, int ldc2, int ncols, const int* status);
 int qrd_th_colssq(void* stream, const double* X, int ldx, int p, int p_add, int cols, double* acc, const int* status);
 
-/* one-sided block Jacobi SVD (qr_svd.hip, called from qr_svd.c only -- as above, the stub device layer does not have them).
+/* one-sided block Jacobi SVD (qr_svd.hip, called from qr_svd.c only).
  * qrd_jsvd_round: one round of the tournament, one workgroup per block pair: pairs = 2 npairs device ints (p, q) in units of
  * QRD_JSVD_BLOCK columns (p == q: the self-pair of a one-block matrix); G is r x n (ldg), V (n x n, ldv) receives the same rotations
  * (NULL: none accumulated); slots[i] = the measure max |s_ij| / sqrt(s_ii s_jj) pair i met BEFORE it rotated; a pair at or below tol
@@ -274,7 +274,7 @@ int qrd_jsvd_normalise(void* stream, double* G, int ldg, int r, int n, const dou
 int qrd_jsvd_pinv_scale(void* stream, const double* T1, double* T2, int n, int nrhs, const double* sig, double rc);
 int qrd_jsvd_rt(void* stream, const double* A, int lda, int n, double* W, int ldw);
 
-/* column-pivoted factorisation (qr_pivot.hip, called from qr_pivot.c only -- as above, the stub device layer does not have them).
+/* column-pivoted factorisation (qr_pivot.hip, called from qr_pivot.c only).
  * The workspace of a plan of n columns: qrd_pivot_ws_doubles(n) doubles and qrd_pivot_ws_ints(n) ints, bound by qrd_pivot_ws_bind.
  *   F      ldf x QRD_PIVOT_NBP   LAPACK dlaqps' F of the current panel (row = column of the matrix)
  *   FT     its trailing rows transposed, for the general product when the block update cannot go to qrd_gemm_nt
@@ -298,7 +298,7 @@ int qrd_pivot_column(void* stream, const qrd_pivot_ws* w, double* A, int lda, in
 int qrd_pivot_scatter(void* stream, const double* B, int ldb, int n, int nrhs, int r, const int* jpvt, double* S);
 int qrd_pivot_resid(void* stream, const double* B, int ldb, int r0, int m, int nrhs, double* resid);
 
-/* batched small matrices (qr_batched.hip, called from qr_batched.c only -- as above, the stub device layer does not have them).  Matrix
+/* batched small matrices (qr_batched.hip, called from qr_batched.c only).  Matrix
  * q of a batch is at base + q * stride (doubles), column-major.  The route is chosen from (m, columns held) alone: one wave per matrix
  * for m <= 64 and <= 32 columns (qrd_b_wave_route), else one workgroup per matrix with the matrix in LDS.
  * qrd_b_max_rows: the rows that fit for every column count of ncols' class (<= 32: 512, <= 64: 256; 0: too many columns);
@@ -338,8 +338,8 @@ int qrd_b_jsvd(void* stream, const double* A, int m, int n, int lda, size_t stri
                size_t strideS, double* U, int ldu, size_t strideU, double* V, int ldv, size_t strideV, int* rank, int* sweeps, int* info,
                int max_sweeps, int batch);
 
-/* batched row append / removal (qr_batched_update.hip, called from qr_batched_update.c only -- as above, the stub device layer does not
- * have them; mi355x_qr.h section 8d).  Per member the n x n triangle R (and Z, n x nrhs, riding along) stacked on a block of p rows of
+/* batched row append / removal (qr_batched_update.hip, called from qr_batched_update.c only;
+ * mi355x_qr.h section 8d).  Per member the n x n triangle R (and Z, n x nrhs, riding along) stacked on a block of p rows of
  * n + nrhs columns, of which rows [0, p_add) count +1 and rows [p_add, p) count -1.  The block is described by two pairs of buffers: entry
  * (i, c) of its first n columns is A0[q sA0 + c lda0 + i] for i < p_add and A1[q sA1 + c lda1 + (i - p_add)] otherwise, and C0 / C1 hold
  * the last nrhs columns in the same way (a pair that covers no row is not referenced).
@@ -371,8 +371,8 @@ int qrd_bu_apply(void* stream, int trans_t, const double* V, int p, int p_add, i
 int qrd_bu_solve_prep(void* stream, const double* Z, int n, int nrhs, double* X, int ldx, size_t strideX, const double* rss, double* resid,
                       size_t strideresid, int batch);
 
-/* batched minimum-norm solves (qr_batched_minnorm.hip, called from qr_batched_minnorm.c only -- as above, the stub device layer does not
- * have them; mi355x_qr.h section 8e).  (m, n) is the shape of the tall matrix F that is factored, m >= n.
+/* batched minimum-norm solves (qr_batched_minnorm.hip, called from qr_batched_minnorm.c only;
+ * mi355x_qr.h section 8e).  (m, n) is the shape of the tall matrix F that is factored, m >= n.
  * qrd_bm_fused: factor F and solve F^T X = B for minimum norm in one launch; n + nrhs columns are held (qrd_b_fits(m, n + nrhs)), the
  * route is qrd_b_wave_route(m, n + nrhs).  tr == 0: F is A (lda >= m); tr != 0: F is the transpose of A (n x m, lda >= n), read
  * through the transposed index map.  The factors go to F (ldf >= m; A itself for the in-place call) in qrd_b_geqrf's layout, bitwise
@@ -386,8 +386,8 @@ int qrd_bm_apply(void* stream, const double* A, int m, int n, int lda, size_t st
                  int ldb, size_t strideB, int* info, int batch);
 int qrd_bm_transpose(void* stream, const double* S, int rows, int cols, int lds, size_t strideS, double* D, int ldd, size_t strideD, int batch);
 
-/* batched damped least squares (qr_batched_damped.hip, called from qr_batched_damped.c only -- as above, the stub device layer does not
- * have them; mi355x_qr.h section 8f).  Per member and per lambda_k, k < nlam: the n rows of lambda_k diag(d) eliminated against the
+/* batched damped least squares (qr_batched_damped.hip, called from qr_batched_damped.c only;
+ * mi355x_qr.h section 8f).  Per member and per lambda_k, k < nlam: the n rows of lambda_k diag(d) eliminated against the
  * triangle R with Z riding along, then R~ x = z~.
  *   R (n x n, ldr >= n; the upper triangle is read), Z (zrows x nrhs, ldz >= zrows >= n: rows 0 .. n-1 are the top of Q^T B, the squares
  *   of rows n .. zrows-1 are added to rss), rss (nrhs per member, packed; NULL: 0), jpvt (n per member, sj apart; NULL: the identity; S

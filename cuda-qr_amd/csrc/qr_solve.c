@@ -8,8 +8,8 @@
  *   qr_gels_dev      geqrf -> ormqr('T') -> solve_r, all on the plan's stream
  *   qr_lstsq         the same on host pointers, through the plan cache of the host-pointer entry points (qr_host.c)
  *
- * Kept out of qr_host.c on purpose: the sanitizer and stub builds compile qr_host.c against a stub device layer that has none of the
- * launch wrappers called here. */
+ * Kept out of qr_host.c on purpose: the sanitizer and order builds of the host schedule link qr_host.c alone against the stub device
+ * layer; the units_* builds link every unit against it (tests/c/qrd_stub_units.c holds the launch wrappers called here). */
 #define _POSIX_C_SOURCE 200809L
 #include <math.h>
 #include <stdint.h>
@@ -69,7 +69,8 @@ int qr_build_t_dev(qr_plan* p, const double* dA, int m, int n, int lda, const do
 {
     if (!p || !dA || !dtau || !dT || n < 1 || m < n || m > p->m || n > p->n || lda < m || ldt < p->nb) return QR_E_ARG;
     use_set0(p);
-    CHECK(qrd_memset(p->stream, dT, 0, sizeof(double) * (size_t) ldt * n));   /* zeros below each block's diagonal */
+    /* zeros below each block's diagonal: the nb x n block and no more (ldt * n doubles would run ldt - nb past its last column) */
+    CHECK(qrd_zero_block(p->stream, dT, ldt, p->nb, n));
     for (int k = 0; k < n; k += p->nb) {
         const int w = imin(p->nb, n - k);
         CHECK(panel_t(p, dA, lda, dtau, k, m - k, w, dT + (size_t) k * ldt, ldt, NULL));

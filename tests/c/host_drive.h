@@ -1,5 +1,5 @@
 /* host_drive.h -- TEST-ONLY helpers shared by the drivers of the C host layer over the stub device layer (host_sanitize.c: the
- * sanitizer run; host_order.c: one schedule configuration per process for the stream-order check). */
+ * sanitizer run; host_order.c: one schedule configuration per process for the stream-order check; host_units.c: the per-interface units). */
 #ifndef HOST_DRIVE_H
 #define HOST_DRIVE_H
 #include <pthread.h>
@@ -11,6 +11,46 @@
 long qrd_stub_launches(void);
 long qrd_stub_stalls(void);
 int qrd_stub_live_allocations(void);
+
+/* ---- the drivers of the per-interface units (host_units.c): the stub's hooks, caller-side buffers, the call macros ---- */
+int qrd_malloc(void** p, size_t bytes);
+int qrd_free(void* p);
+long qrd_stub_order_reports(void);
+int qrd_stub_fail_take(void);
+long qrd_stub_alloc_count(void);
+int qrd_stub_alloc_site(long k, size_t* bytes, const char** func, const char** expr);
+void qrd_stub_script(const char* entry, const double* v, int n);
+void qrd_stub_set_diag(double d);
+void qrd_stub_set_info(int v);
+void qrd_stub_guard(const void* p, size_t bytes);
+
+/* caller-side device buffers: straight from the stub (not counted as the library's), exactly the size asked, freed by dev_free_all */
+static void* g_dev_buf[512] __attribute__((unused));
+static int g_dev_nbuf __attribute__((unused));
+static inline void* dev_bytes(size_t bytes)
+{
+    void* p = NULL;
+    if (g_dev_nbuf == 512 || qrd_malloc(&p, bytes)) { fprintf(stderr, "driver: out of device buffers\n"); exit(1); }
+    return g_dev_buf[g_dev_nbuf++] = p;
+}
+/* `batch` blocks rows x cols at leading dimension ld, stride doubles apart: the documented minimum, to the last element of the last block */
+static inline double* dev_blocks(long rows, long cols, long ld, long batch, long stride)
+{ return (double*) dev_bytes(sizeof(double) * (size_t) ((batch - 1) * stride + (cols - 1) * ld + rows)); }
+static inline double* dev_block(long rows, long cols, long ld) { return dev_blocks(rows, cols, ld, 1, 0); }
+static inline double* dev_vec(long n) { return dev_block(n, 1, n); }
+static inline int* dev_ints(long n) { return (int*) dev_bytes(sizeof(int) * (size_t) n); }
+static inline void dev_free_all(void) { while (g_dev_nbuf) qrd_free(g_dev_buf[--g_dev_nbuf]); }
+
+/* CALL(x): x must return 0.  Under QRD_STUB_FAIL_MALLOC a call that returns QR_E_ALLOC after the injected failure fired is made once more,
+ * on the same plan and handles, and must then complete.  CALLS(setup, x, want): `setup` runs before every attempt (scripted words), the
+ * call must return `want`.  ARG(x): QR_E_ARG, and nothing was launched. */
+static int g_fail_hits __attribute__((unused));
+#define CALLS(setup, x, want) do { setup; int rc_ = (x); if (rc_ == QR_E_ALLOC && qrd_stub_fail_take()) { ++g_fail_hits; setup; rc_ = (x); } \
+    if (rc_ != (want)) { fprintf(stderr, "%s:%d: %s -> %d (%s), expected %d\n", __FILE__, __LINE__, #x, rc_, qr_strerror(rc_), (int) (want)); exit(1); } } while (0)
+#define CALLX(x, want) CALLS((void) 0, x, want)
+#define CALL(x) CALLS((void) 0, x, 0)
+#define ARG(x) do { const long l0_ = qrd_stub_launches(); const int rc_ = (x); if (rc_ != QR_E_ARG || qrd_stub_launches() != l0_) { \
+    fprintf(stderr, "%s:%d: %s -> %d with %ld launches, expected QR_E_ARG and none\n", __FILE__, __LINE__, #x, rc_, qrd_stub_launches() - l0_); exit(1); } } while (0)
 
 #define OK(x) do { int rc_ = (x); if (rc_) { fprintf(stderr, "%s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #x, rc_, qr_strerror(rc_)); exit(1); } } while (0)
 

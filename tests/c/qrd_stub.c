@@ -23,6 +23,9 @@
  *           blocking copies, which end in a host sync); tile-padding over-reads of the real loaders are not modelled.
  *           Test hooks: QRD_STUB_SKIP_WAIT=k lets the k-th stream_wait_event of the process return without joining; qrd_stub_wait_at
  *           is stream_wait_event with the caller's site (the `order` build of the Makefile routes qr_host.c's calls through it).
+ *           QRD_STUB_FAIL_MALLOC=k / QRD_STUB_SHRINK_MALLOC=k: see qrd_stub_malloc_at; qrd_stub_guard: a block no launch may write.
+ * The launches of the per-interface host units (qr_solve.c ... qr_batched_lm.c) and the scripted device words that drive their host
+ * loops are in qrd_stub_units.c, included at the end of this file.
  * It is never linked into libmi355xqr.so and nothing under cuda-qr_amd/ refers to it. */
 #define _POSIX_C_SOURCE 200809L
 #include <pthread.h>
@@ -165,20 +168,27 @@ static void order_access(int ai, const char* what, size_t off, size_t run, size_
 }
 
 /* `ncols` runs of `run` bytes, `stride` bytes apart, at p: inside ONE live allocation?  Then stamp them for the order model */
+static const char* g_guard_p;      /* qrd_stub_guard: a block no launch may write while it is set (a rollback must leave it alone) */
+static size_t g_guard_n;
+void qrd_stub_guard(const void* p, size_t bytes) { g_guard_p = (const char*) p; g_guard_n = p ? bytes : 0; }
 static void chk_bytes(const char* what, const void* p, size_t run, size_t stride, long ncols, int mode)
 {
-    const size_t bytes = stride * (size_t) (ncols - 1) + run, bytes8 = (bytes + 7) & ~(size_t) 7;
+    const size_t bytes = stride * (size_t) (ncols - 1) + run;      /* (allocations are whole multiples of 8 bytes: no rounding is needed, and a block of ints may start between two) */
     const char* c = (const char*) p;
     int ok = 0;
+    if (g_guard_n && (mode & ACC_W) && c < g_guard_p + g_guard_n && g_guard_p < c + bytes) {
+        fprintf(stderr, "qrd_stub: %s: writes %p + %zu bytes, inside the guarded block %p + %zu\n", what, p, bytes, (const void*) g_guard_p, g_guard_n);
+        abort();
+    }
     pthread_mutex_lock(&g_mu);
     for (int i = 0; i < g_nalloc && !ok; ++i)
-        if (c >= g_alloc[i].p && c + bytes8 <= g_alloc[i].p + g_alloc[i].n) {
+        if (c >= g_alloc[i].p && c + bytes <= g_alloc[i].p + g_alloc[i].n) {
             ok = 1;
             order_access(i, what, (size_t) (c - g_alloc[i].p), run, stride, ncols, mode);
         }
     ++g_launches;
     pthread_mutex_unlock(&g_mu);
-    if (!ok) die(what, p, bytes8);
+    if (!ok) die(what, p, bytes);
 }
 /* column-major block rows x cols (doubles) with leading dimension ld at p */
 static void chk(const char* what, const void* p, long ld, long rows, long cols, int mode)
@@ -212,18 +222,51 @@ int qrd_panel_tsqr_init(void) { return 0; }
 int qrd_leaf_fused_init(void) { return 0; }
 int qrd_panel_fused_init(void) { return 0; }
 
-int qrd_malloc(void** p, size_t bytes)
+/* The LIBRARY's allocations of the process, in call order (tests/c/units_sites.h routes the qrd_malloc calls of the host units through
+ * qrd_stub_malloc_at with their site: the calling function and the text of the pointer expression).  A call without a site, or from
+ * qr_device_malloc, is the caller's own buffer and is not counted.  QRD_STUB_FAIL_MALLOC=k: the k-th counted allocation fails, once, with
+ * QR_E_ALLOC's value (-102; the real layer hands hipErrorOutOfMemory up the same way) -- qrd_stub_fail_take tells the driver that it did;
+ * QRD_STUB_SHRINK_MALLOC=k: the k-th one is 8 bytes shorter than asked (tests/test_units_stub.py: every workspace is checked and tight). */
+#define MAXSITE 4096
+static struct { size_t bytes; const char *func, *expr; } g_site[MAXSITE];
+static long g_nsite, g_fail_at = -1, g_shrink_at = -1;
+static int g_fail_fired;
+int qrd_stub_malloc_at(void** p, size_t bytes, const char* func, const char* expr)
 {
     if (!p) return 1;
-    const size_t n = (bytes + 7) & ~(size_t) 7;
-    char* q = (char*) calloc(1, n ? n : 8);
+    size_t n = (bytes + 7) & ~(size_t) 7;
+    if (!n) n = 8;
+    const int counted = func && strcmp(func, "qr_device_malloc") != 0;
+    pthread_mutex_lock(&g_mu);
+    if (g_fail_at < 0) {
+        const char *f = getenv("QRD_STUB_FAIL_MALLOC"), *s = getenv("QRD_STUB_SHRINK_MALLOC");
+        g_fail_at = f ? atol(f) : 0; g_shrink_at = s ? atol(s) : 0;
+    }
+    long k = 0;
+    if (counted) {
+        if (g_nsite < MAXSITE) { g_site[g_nsite].bytes = bytes; g_site[g_nsite].func = func; g_site[g_nsite].expr = expr; }
+        k = ++g_nsite;
+    }
+    if (k && k == g_fail_at) { g_fail_fired = 1; pthread_mutex_unlock(&g_mu); *p = NULL; return -102; }
+    const size_t keep = (k && k == g_shrink_at) ? n - 8 : n;      /* what the bounds check believes; the host block keeps its size */
+    pthread_mutex_unlock(&g_mu);
+    char* q = (char*) calloc(1, n);
     if (!q) return 2;
     pthread_mutex_lock(&g_mu);
     if (g_nalloc == MAXA) { pthread_mutex_unlock(&g_mu); free(q); return 2; }
     memset(&g_alloc[g_nalloc], 0, sizeof g_alloc[0]);
-    g_alloc[g_nalloc].p = q; g_alloc[g_nalloc].n = n ? n : 8; g_alloc[g_nalloc].prune_at = 64; ++g_nalloc;
+    g_alloc[g_nalloc].p = q; g_alloc[g_nalloc].n = keep; g_alloc[g_nalloc].prune_at = 64; ++g_nalloc;
     pthread_mutex_unlock(&g_mu);
     *p = q;
+    return 0;
+}
+int qrd_malloc(void** p, size_t bytes) { return qrd_stub_malloc_at(p, bytes, NULL, NULL); }
+int qrd_stub_fail_take(void) { pthread_mutex_lock(&g_mu); const int f = g_fail_fired; g_fail_fired = 0; pthread_mutex_unlock(&g_mu); return f; }
+long qrd_stub_alloc_count(void) { pthread_mutex_lock(&g_mu); const long n = g_nsite; pthread_mutex_unlock(&g_mu); return n; }
+int qrd_stub_alloc_site(long k, size_t* bytes, const char** func, const char** expr)
+{
+    if (k < 1 || k > g_nsite || k > MAXSITE) return 1;
+    *bytes = g_site[k - 1].bytes; *func = g_site[k - 1].func; *expr = g_site[k - 1].expr;
     return 0;
 }
 /* every stream of the calling thread's device (the NULL stream too) joins the host thread: hipDeviceSynchronize, and hipFree */
@@ -757,3 +800,6 @@ int qrd_allgather_f64(void* comm, void* stream, const double* send, double* recv
     { const char* e = getenv("QRD_STUB_GATHER_MS"); if (e) g_stub_after_gather = atof(e); }
     return 0;
 }
+
+/* the device layer of the per-interface host units (least squares down to batched Levenberg-Marquardt): same helpers, a file of its own */
+#include "qrd_stub_units.c"
