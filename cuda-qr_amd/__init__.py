@@ -249,6 +249,22 @@ _sig("qr_lm_batched_running", C.c_int, _vp, C.POINTER(C.c_int))
 _sig("qr_lm_batched_destroy", C.c_int, _vp)
 _sig("qr_lm_step_batched_dev", C.c_int, _vp, _vp, C.c_int, _ll, _vp, C.c_int, C.c_int, _ll, _vp, _vp, _ll)
 _sig("qr_lstsq_lm_batched", C.c_int, LM_FCN, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(LmOptions), _dp, _ip, _ip, _ip, _ip)
+class LmBoundedState(C.Structure):
+    """qr_lmb_batched_state: device addresses"""
+    _doubles = LmState._doubles + ("lo", "hi", "alpha")
+    _ints = LmState._ints + ("peg", "clipped")
+    _fields_ = [(k, C.c_void_p) for k in LmState._doubles + LmState._ints + ("lo", "hi", "alpha", "peg", "clipped")]
+
+
+_sig("qr_lmb_batched_create", C.c_int, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmOptions))
+_sig("qr_lmb_batched_start_dev", C.c_int, _vp, _vp, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _ll)
+_sig("qr_lmb_batched_step_dev", C.c_int, _vp, _vp, C.c_int, _ll, _vp, C.c_int, _ll)
+_sig("qr_lmb_batched_update_dev", C.c_int, _vp, _vp, C.c_int, _ll)
+_sig("qr_lmb_batched_view", C.c_int, _vp, C.POINTER(LmBoundedState))
+_sig("qr_lmb_batched_running", C.c_int, _vp, C.POINTER(C.c_int))
+_sig("qr_lmb_batched_destroy", C.c_int, _vp)
+_sig("qr_lstsq_lm_bounded_batched", C.c_int, LM_FCN, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(LmOptions), _dp, _ip, _ip, _ip,
+     _ip)
 _sig("qr_irls_batched_max_rows", C.c_int, C.c_int)
 _sig("qr_irls_batched_dev", C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _ll, C.c_double,
      C.c_int, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -964,10 +980,30 @@ def lm_options(**options):
     return o
 
 
-def lstsq_lm_batched(fun, jac, x0, D=None, m=None, **options):
+def _lm_bounds_host(bounds, batch, n, who):
+    """bounds = (lo, hi) -> two packed (batch, n) arrays or None; each of lo, hi: None (unbounded), a scalar, (n,) or (batch, n)"""
+    try:
+        lo, hi = bounds
+    except (TypeError, ValueError):
+        raise QRError(f"{who}: bounds must be a pair (lo, hi)", QR_E_ARG)
+    out = []
+    for v in (lo, hi):
+        if v is None:
+            out.append(None)
+            continue
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim == 2 and v.shape != (batch, n) or v.ndim == 1 and v.shape != (n,) or v.ndim > 2:
+            raise QRError(f"{who}: a bound must be a scalar, ({n},) or ({batch}, {n}), got {v.shape}", QR_E_ARG)
+        out.append(np.ascontiguousarray(np.broadcast_to(v, (batch, n))))
+    return out
+
+
+def lstsq_lm_batched(fun, jac, x0, D=None, m=None, bounds=None, **options):
     """min ||f_q(x)|| for every member by Levenberg-Marquardt (MINPACK lmder's iteration, the loop of every member on the device) through
     qr_lstsq_lm_batched.  fun: numpy (batch, n) -> (batch, m); jac: (batch, n) -> (batch, m, n); x0: (batch, n); D: the scaling of mode 2
     (n,) or (batch, n); m: the number of residuals (None: fun is called once on x0 to find it); options: the fields of qr_lm_options.
+    bounds: None, or (lo, hi) for lo <= x <= hi through qr_lstsq_lm_bounded_batched (mi355x_qr.h section 8n; each of lo, hi: None, a
+    scalar, (n,) or (batch, n); entries may be infinite).
     Returns (X, fnorm, nfev, njev, status, info): status is MINPACK's info (1 .. 8), or -1 for a member with an info word (which does
     not raise)."""
     x0 = np.asarray(x0, dtype=np.float64)
@@ -984,6 +1020,8 @@ def lstsq_lm_batched(fun, jac, x0, D=None, m=None, **options):
         if D.shape != (batch, n):
             raise QRError(f"lstsq_lm_batched: D must be ({n},) or ({batch}, {n}), got {D.shape}", QR_E_ARG)
         D = np.ascontiguousarray(D)
+    if bounds is not None:
+        lo, hi = _lm_bounds_host(bounds, batch, n, "lstsq_lm_batched")
     raised = []
 
     def model(_user, what, X, nb, F, J):
@@ -1001,12 +1039,17 @@ def lstsq_lm_batched(fun, jac, x0, D=None, m=None, **options):
     X = np.ascontiguousarray(x0).copy()
     fnorm = np.zeros(batch)
     nfev, njev, status, info = (np.zeros(max(batch, 1), dtype=np.intc) for _ in range(4))
-    rc = lib.qr_lstsq_lm_batched(LM_FCN(model), None, m, n, batch, _p(X), None if D is None else _p(D), C.byref(o), _p(fnorm),
-                                 nfev.ctypes.data_as(_ip), njev.ctypes.data_as(_ip), status.ctypes.data_as(_ip), info.ctypes.data_as(_ip))
+    tail = (C.byref(o), _p(fnorm), nfev.ctypes.data_as(_ip), njev.ctypes.data_as(_ip), status.ctypes.data_as(_ip), info.ctypes.data_as(_ip))
+    Dp = None if D is None else _p(D)
+    if bounds is None:
+        name, rc = "qr_lstsq_lm_batched", lib.qr_lstsq_lm_batched(LM_FCN(model), None, m, n, batch, _p(X), Dp, *tail)
+    else:
+        name, rc = "qr_lstsq_lm_bounded_batched", lib.qr_lstsq_lm_bounded_batched(
+            LM_FCN(model), None, m, n, batch, _p(X), None if lo is None else _p(lo), None if hi is None else _p(hi), Dp, *tail)
     if raised:
         raise raised[0]
     if rc != QR_E_SINGULAR:
-        check(rc, "qr_lstsq_lm_batched")
+        check(rc, name)
     return X, fnorm, nfev[:batch].astype(np.int64), njev[:batch].astype(np.int64), status[:batch].astype(np.int64), info[:batch].astype(np.int64)
 
 
@@ -1863,6 +1906,7 @@ class LmBatched:
     start(dX0); then per round: fill J and f at state()["x"], step(dJ, dF); fill f at state()["xtrial"], update(dFtrial); running()
     is the one call that waits on the host.  The calls run on the plan's stream: model code in torch runs there too inside
     `with torch.cuda.stream(torch.cuda.ExternalStream(plan.stream))`.  The plan must stay open for as long as the solver is used."""
+    _state = LmState
 
     def __init__(self, plan, m, n, batch, **options):
         self.h = None
@@ -1912,12 +1956,13 @@ class LmBatched:
             dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
             ptr = self.view()
             out = {}
-            for k in LmState._doubles + LmState._ints:
-                shape = (self.batch, self.n) if k in ("x", "xtrial", "D") else (self.batch,)
+            S = self._state
+            for k in S._doubles + S._ints:
+                shape = (self.batch, self.n) if k in ("x", "xtrial", "D", "lo", "hi", "peg") else (self.batch,)
                 if self.batch == 0:
-                    out[k] = torch.empty(shape, dtype=torch.float64 if k in LmState._doubles else torch.int32, device=dev)
+                    out[k] = torch.empty(shape, dtype=torch.float64 if k in S._doubles else torch.int32, device=dev)
                 else:
-                    out[k] = torch.as_tensor(_RawDeviceArray(ptr[k], shape, "<f8" if k in LmState._doubles else "<i4"), device=dev)
+                    out[k] = torch.as_tensor(_RawDeviceArray(ptr[k], shape, "<f8" if k in S._doubles else "<i4"), device=dev)
             self._views = out
         return self._views
 
@@ -1928,12 +1973,83 @@ class LmBatched:
         return c.value
 
 
-def lm_batched(fun, jac, x0, *, D=None, check_every=1, plan=None, **options):
+class LmBoundedBatched(LmBatched):
+    """qr_lmb_batched wrapper: LmBatched's loop with box bounds lo <= x <= hi (mi355x_qr.h section 8n).  The protocol is LmBatched's;
+    start takes the bounds, and state() has lo, hi (batch, n) float64, peg (batch, n) int32, alpha (batch,) float64 and clipped (batch,)
+    int32 as well."""
+    _state = LmBoundedState
+
+    def __init__(self, plan, m, n, batch, **options):
+        self.h = None
+        self.options = lm_options(**options)
+        h = _vp()
+        check(lib.qr_lmb_batched_create(C.byref(h), plan.h, m, n, batch, C.byref(self.options)), "qr_lmb_batched_create")
+        self.h, self.plan, self.m, self.n, self.batch = h, plan, m, n, batch
+        self._views = None
+
+    def close(self):
+        if self.h and lib is not None and self.plan.h:
+            lib.qr_lmb_batched_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def start(self, dX0, ldx=None, strideX=None, dD0=None, strideD=None, dLo=None, strideLo=None, dHi=None, strideHi=None):
+        """x <- dX0, the scaling of mode 2 as in LmBatched.start; dLo, dHi: the bounds, n per member (stride 0: one vector shared by all
+        members; None: that side is unbounded)"""
+        ldx = self.n if ldx is None else ldx
+        check(lib.qr_lmb_batched_start_dev(self.h, _dptr(dX0), ldx, ldx if strideX is None else strideX, _dptr(dD0),
+                                           self.n if strideD is None else strideD, _dptr(dLo), self.n if strideLo is None else strideLo,
+                                           _dptr(dHi), self.n if strideHi is None else strideHi), "qr_lmb_batched_start_dev")
+
+    def step(self, dJ, dF, ldj=None, strideJ=None, ldf=None, strideF=None):
+        """the peg on dJ and dF, then LmBatched.step's three launches with the step cut to the box"""
+        ldj = self.m if ldj is None else ldj
+        ldf = self.m if ldf is None else ldf
+        check(lib.qr_lmb_batched_step_dev(self.h, _dptr(dJ), ldj, ldj * self.n if strideJ is None else strideJ, _dptr(dF), ldf,
+                                          ldf if strideF is None else strideF), "qr_lmb_batched_step_dev")
+
+    def update(self, dFtrial, ldf=None, strideF=None):
+        ldf = self.m if ldf is None else ldf
+        check(lib.qr_lmb_batched_update_dev(self.h, _dptr(dFtrial), ldf, ldf if strideF is None else strideF), "qr_lmb_batched_update_dev")
+
+    def view(self):
+        v = LmBoundedState()
+        check(lib.qr_lmb_batched_view(self.h, C.byref(v)), "qr_lmb_batched_view")
+        return {k: getattr(v, k) for k, _ in LmBoundedState._fields_}
+
+    def running(self):
+        c = C.c_int()
+        check(lib.qr_lmb_batched_running(self.h, C.byref(c)), "qr_lmb_batched_running")
+        return c.value
+
+
+def _lm_bounds_dev(bounds, batch, n, device):
+    """bounds = (lo, hi) -> two packed (batch, n) device tensors or None"""
+    import torch
+    try:
+        lo, hi = bounds
+    except (TypeError, ValueError):
+        raise QRError("lm_batched: bounds must be a pair (lo, hi)", QR_E_ARG)
+    out = []
+    for v in (lo, hi):
+        if v is None:
+            out.append(None)
+            continue
+        v = torch.as_tensor(v, dtype=torch.float64, device=device)
+        if v.dim() > 2 or (v.dim() == 2 and tuple(v.shape) != (batch, n)) or (v.dim() == 1 and tuple(v.shape) != (n,)):
+            raise QRError(f"lm_batched: a bound must be a scalar, ({n},) or ({batch}, {n}), got {tuple(v.shape)}", QR_E_ARG)
+        out.append(v.expand(batch, n).contiguous())
+    return out
+
+
+def lm_batched(fun, jac, x0, *, D=None, check_every=1, plan=None, bounds=None, **options):
     """min ||f_q(x)|| for every member by Levenberg-Marquardt with the model in torch: fun maps x (batch, n) to f (batch, m) and jac to
     J (batch, m, n), both on device tensors; x0: (batch, n) on the device; D: the scaling of mode 2, (n,) or (batch, n).  The model runs
     on the plan's stream between the two device calls of a round, the wrapper does the layout copy of J, and running() -- the only host
-    wait -- is polled every `check_every` rounds.  options: the fields of qr_lm_options.  Returns a dict of torch tensors: the state of
-    LmBatched.state() (copies), x first."""
+    wait -- is polled every `check_every` rounds.  options: the fields of qr_lm_options.  bounds: None, or (lo, hi) for lo <= x <= hi
+    through LmBoundedBatched (each of lo, hi: None, a scalar, (n,) or (batch, n); entries may be infinite).  Returns a dict of torch
+    tensors: the state of LmBatched.state() (copies; LmBoundedBatched.state() with bounds), x first."""
     import torch
     if x0.dim() != 2:
         raise QRError(f"lm_batched: x0 must be (batch, n), got {tuple(x0.shape)}", QR_E_ARG)
@@ -1946,6 +2062,8 @@ def lm_batched(fun, jac, x0, *, D=None, check_every=1, plan=None, **options):
         if tuple(D.shape) != (batch, n):
             raise QRError(f"lm_batched: D must be ({n},) or ({batch}, {n}), got {tuple(D.shape)}", QR_E_ARG)
         D = D.contiguous()
+    if bounds is not None:
+        bounds = _lm_bounds_dev(bounds, batch, n, x0.device)
     torch.cuda.synchronize()                  # x0 and D were made on torch's streams; from here on everything runs on the plan's
     x0 = x0.to(torch.float64).contiguous()
     m = int(fun(x0).shape[1])
@@ -1954,23 +2072,26 @@ def lm_batched(fun, jac, x0, *, D=None, check_every=1, plan=None, **options):
     if own:
         plan = Plan(max(m, 1), n)
     try:
-        return _lm_batched_run(plan, fun, jac, x0, D, m, max(int(check_every), 1), options)
+        return _lm_batched_run(plan, fun, jac, x0, D, m, max(int(check_every), 1), options, bounds)
     finally:                                  # (whatever was allocated under the plan's stream is gone before the stream is)
         torch.cuda.synchronize()
         if own:
             plan.close()
 
 
-def _lm_batched_run(plan, fun, jac, x0, D, m, every, options):
+def _lm_batched_run(plan, fun, jac, x0, D, m, every, options, bounds=None):
     import torch
     batch, n = x0.shape
-    lm = LmBatched(plan, m, n, batch, **options)
+    lm = LmBatched(plan, m, n, batch, **options) if bounds is None else LmBoundedBatched(plan, m, n, batch, **options)
     try:
         J = torch.empty((batch, n, m), dtype=torch.float64, device=x0.device)           # member q: J_q column-major
         F = torch.empty((batch, m), dtype=torch.float64, device=x0.device)
         torch.cuda.synchronize()
         with torch.cuda.stream(torch.cuda.ExternalStream(plan.stream)):
-            lm.start(x0, dD0=D)
+            if bounds is None:
+                lm.start(x0, dD0=D)
+            else:
+                lm.start(x0, dD0=D, dLo=bounds[0], dHi=bounds[1])
             st = lm.state(x0.device)
             limit = lm.options.maxfev if lm.options.maxfev > 0 else 100 * (n + 1)     # every round adds 1 to nfev of every running member
             for rounds in range(1, limit + 1 if batch else 1):

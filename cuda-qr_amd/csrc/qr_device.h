@@ -465,6 +465,34 @@ int qrd_blm_start(void* stream, const double* X0, int ldx, size_t sX, const doub
 int qrd_blm_step(void* stream, const qrd_blm_step_args* a);
 int qrd_blm_update(void* stream, const double* Ft, int m, int ldf, size_t sF, int n, int batch, const qrd_blm_state* s, const qrd_blm_opts* o);
 
+/* batched Levenberg-Marquardt with box bounds on x (qr_batched_lmb.hip, called from qr_batched_lmb.c only; mi355x_qr.h section 8n): the
+ * loop above with MPFIT's rules for lo <= x <= hi.  The rules of section 8m are the device code of qr_batched_lm_dev.h in both files.
+ *   qrd_blmb_state: qrd_blm_state, then lo, hi (n per member), peg (n ints per member: -1 held at lo, +1 held at hi, 0 free), alpha (the
+ *   fraction of the step taken) and clipped (alpha < 1), one each.
+ *   qrd_blmb_start: qrd_blm_start, and lo <- Lo (sLo apart, 0: shared; NULL: -inf), hi <- Hi likewise (NULL: +inf).  A member whose
+ *   bounds are no box (lo_j > hi_j or a NaN) or whose x0 lies outside gets info -2 and nothing else of it is written.
+ *   qrd_blmb_peg: before the factorisation, on the unfactored J (m x n, ldj, sJ) and f (m, sF): per running member g_j = sum_i J(i,j) f_i
+ *   for the columns with x_j on a bound, peg_j from its sign, the held columns of J cleared.  One launch, a wave per member.
+ *   qrd_blmb_step: qrd_blm_step, with the step cut to the box between the search and the trial point.  One launch, the routes of
+ *   qrd_blm_step.  qrd_blmb_update: qrd_blm_update without the two tests on the reductions while clipped is set.
+ * batch <= 0: nothing is launched.  -7: shape not taken */
+typedef struct qrd_blmb_state {
+    qrd_blm_state b;
+    double *lo, *hi, *alpha;
+    int *peg, *clipped;
+} qrd_blmb_state;
+typedef struct qrd_blmb_step_args {
+    qrd_bd_args d;
+    qrd_blmb_state s;
+    qrd_blm_opts o;
+} qrd_blmb_step_args;
+int qrd_blmb_start(void* stream, const double* X0, int ldx, size_t sX, const double* D0, size_t sD, const double* Lo, size_t sLo,
+                   const double* Hi, size_t sHi, int n, int batch, const qrd_blmb_state* s, int mode);
+int qrd_blmb_peg(void* stream, double* J, int m, int ldj, size_t sJ, const double* F, size_t sF, int n, int batch, const qrd_blmb_state* s);
+int qrd_blmb_step(void* stream, const qrd_blmb_step_args* a);
+int qrd_blmb_update(void* stream, const double* Ft, int m, int ldf, size_t sF, int n, int batch, const qrd_blmb_state* s,
+                    const qrd_blm_opts* o);
+
 /* batched equality-constrained least squares (qr_batched_lse.hip, called from qr_batched_lse.c only; mi355x_qr.h section 8h).  Per member
  * min |A x - b| subject to C x = d by the null-space method: C^T = Q_c [R_c ; 0], R_c^T y1 = d, A~ = A Q_c, the QR of A~(:, p:n) with
  * A~(:, 0:p) and b - A~(:, 0:p) y1 riding along, R_a y2 = the top of it, x = Q_c [y1 ; y2], resid from the tail, R_c lambda = g.

@@ -85,7 +85,9 @@
  * [0, 4] (planted (a, b, c), zero residual, the start the planted values times 1.2 or 0.8) go through qr_lstsq_lm_batched, the host twin of
  * the batched Levenberg-Marquardt solver: the model runs on the host between the device calls, so the time is dominated by it and by the
  * copies.  Printed: the time, the worst ||x - planted||, the mean and the largest nfev, the number of non-zero info words and a histogram
- * of status.
+ * of status.  With `--box` the fits go through qr_lstsq_lm_bounded_batched with 0 <= a, 0 <= b <= 0.8 planted b and 0 <= c (the rate bound
+ * cuts off the free minimiser; b starts at half its bound): also printed are the fits that end with b on its bound and the entries
+ * outside the box (0).
  *
  * `./qr_device m n --batched count --slide window step` does nothing else either: `count` seeded series of m rows, n unknowns and one
  * right-hand side each (resident in HBM) go through one batched accumulator -- the first window pushed, every later one ONE
@@ -1044,8 +1046,9 @@ static int lm_expdecay(void* user, int what, const double* X, int batch, double*
     return 0;
 }
 
-/* count exponential-decay fits of m points (n = 3) through the host twin of the batched Levenberg-Marquardt solver */
-static int batched_lm_main(int m, int n, int count)
+/* count exponential-decay fits of m points (n = 3) through the host twin of the batched Levenberg-Marquardt solver; box: through the
+ * bounded twin with 0 <= a, 0 <= b <= 0.8 planted b, 0 <= c, the start of b at half its bound */
+static int batched_lm_main(int m, int n, int count, int box)
 {
     if (n != 3 || m < 3 || m > qr_batched_max_rows(4) || count < 1) {
         fprintf(stderr, "--batched count --lm fits a exp(-b t) + c: needs n == 3, 3 <= m <= %d and count >= 1\n", qr_batched_max_rows(4));
@@ -1065,14 +1068,33 @@ static int batched_lm_main(int m, int n, int count)
         for (int i = 0; i < m; i++) y[q * m + i] = xs[3 * q] * exp(-xs[3 * q + 1] * (m > 1 ? 4.0 * i / (m - 1) : 0.0)) + xs[3 * q + 2];
     }
     lm_model M = {m, y};
+    double *lo = NULL, *hi = NULL;
+    if (box) {
+        lo = calloc(3 * nc, sizeof(double));
+        hi = malloc(sizeof(double) * 3 * nc);
+        if (!lo || !hi) { fprintf(stderr, "out of memory\n"); return 1; }
+        for (size_t q = 0; q < nc; q++) { hi[3 * q] = hi[3 * q + 2] = INFINITY; hi[3 * q + 1] = 0.8 * xs[3 * q + 1]; }
+    }
     double el = 0.0;
     for (int t = -1; t < TRIALS; t++) {
         srand(13);
         for (size_t i = 0; i < 3 * nc; i++) X[i] = xs[i] * (rand() & 1 ? 1.2 : 0.8);
+        if (box)
+            for (size_t q = 0; q < nc; q++) X[3 * q + 1] = 0.5 * hi[3 * q + 1];
         const double t0 = now();
-        const int rc = qr_lstsq_lm_batched(lm_expdecay, &M, m, 3, count, X, NULL, NULL, fnorm, nfev, njev, status, info);
-        if (rc && rc != QR_E_SINGULAR) { fprintf(stderr, "qr_lstsq_lm_batched failed: %s\n", qr_strerror(rc)); return 1; }
+        const int rc = box ? qr_lstsq_lm_bounded_batched(lm_expdecay, &M, m, 3, count, X, lo, hi, NULL, NULL, fnorm, nfev, njev, status, info)
+                           : qr_lstsq_lm_batched(lm_expdecay, &M, m, 3, count, X, NULL, NULL, fnorm, nfev, njev, status, info);
+        if (rc && rc != QR_E_SINGULAR) { fprintf(stderr, "%s failed: %s\n", box ? "qr_lstsq_lm_bounded_batched" : "qr_lstsq_lm_batched", qr_strerror(rc)); return 1; }
         if (t >= 0) el += now() - t0;
+    }
+    if (box) {                    /* the planted x is outside the box: what counts is the box and the bound the fits end on */
+        size_t onb = 0, out = 0;
+        for (size_t q = 0; q < nc; q++) {
+            onb += X[3 * q + 1] == hi[3 * q + 1];
+            for (int j = 0; j < 3; j++) out += !(X[3 * q + j] >= lo[3 * q + j] && X[3 * q + j] <= hi[3 * q + j]);
+        }
+        printf(" box: 0 <= a, 0 <= b <= 0.8 planted b, 0 <= c: %zu of %d fits end with b on its bound, %zu entries outside the box\n", onb, count, out);
+        free(lo); free(hi);
     }
     int hist[10] = {0}, most = 0, failed = 0;
     double worst = 0.0, mean = 0.0;
@@ -1603,7 +1625,7 @@ static int batched_stats_main(int m, int n, int count)
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --lsei mg [neq] | --robust frac | --stats | --lm]"); return 1; }
+    if (argc < 3) { puts("Usage: ./qr_device m n [--compare] [--pivot] | ./qr_device m n --minnorm   (m <= n) | ./qr_device m n --append [chunk_rows] | ./qr_device m n --svd | ./qr_device m n --slide window step | ./qr_device m n --batched count [--pivot [rank] | --svd | --slide window step | --minnorm | --damped nlam | --trust frac | --lse p | --bvls | --lsei mg [neq] | --robust frac | --stats | --lm [--box]]"); return 1; }
     int compare = 0, pivot = 0, minnorm = 0;
     for (int i = 3; i < argc; i++)
         if (strcmp(argv[i], "--append") == 0) return append_main(atoi(argv[1]), atoi(argv[2]), i + 1 < argc ? atoi(argv[i + 1]) : 4096);
@@ -1642,7 +1664,11 @@ int main(int argc, char** argv)
                     return batched_lsei_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), k + 1 < argc ? atoi(argv[k + 1]) : 1,
                                              k + 2 < argc ? atoi(argv[k + 2]) : 0);
             for (int k = 3; k < argc; k++)
-                if (strcmp(argv[k], "--lm") == 0) return batched_lm_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
+                if (strcmp(argv[k], "--lm") == 0) {
+                    int box = 0;
+                    for (int b = 3; b < argc; b++) box |= strcmp(argv[b], "--box") == 0;
+                    return batched_lm_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]), box);
+                }
             for (int k = 3; k < argc; k++)
                 if (strcmp(argv[k], "--bvls") == 0) return batched_bvls_main(atoi(argv[1]), atoi(argv[2]), atoi(argv[i + 1]));
             for (int k = 3; k < argc; k++)

@@ -1656,6 +1656,79 @@ int qr_lm_step_batched_dev(qr_lm_batched* lm, const double* dR, int ldr, long lo
 int qr_lstsq_lm_batched(qr_lm_fcn fcn, void* user, int m, int n, int batch, double* X, const double* D, const qr_lm_options* opt,
                         double* fnorm, int* nfev, int* njev, int* status, int* info);
 
+/* ---------------------------------------------------------------------------------------------
+ * 8n. Batched Levenberg-Marquardt with box bounds on x: section 8m's loop for every member of a batch,
+ *
+ *         min |f(x)|_2  subject to  lo <= x <= hi,      shapes as in section 8m,
+ *
+ * for the users of section 8m whose parameters have simple bounds: an amplitude >= 0, a width > 0, a joint inside its limits, a parameter
+ * held fixed (lo_j == hi_j).  Entries of lo and hi may be -inf and +inf.  Clipping the trial point between section 8m's two calls is the
+ * wrong answer (its prered then belongs to a step that was not taken); the rules below sit inside the step.  They are MPFIT's (Markwardt's
+ * extension of MINPACK to bounds) with two corrections, marked (*).  The protocol, the phase flag, the layout, the stride rules, the
+ * options and the routes are section 8m's, with its words; section 8m itself is unchanged, and with every bound infinite every state array
+ * below is bitwise section 8m's after every call (both run the same device code).
+ *
+ *     qr_lmb_batched_start_dev(lm, dX0, ..., dLo, ..., dHi, ...);
+ *     repeat:  fill J(x) and f(x) at state.x;      qr_lmb_batched_step_dev(lm, dJ, ..., dF, ...);
+ *              fill f(xtrial) at state.xtrial;     qr_lmb_batched_update_dev(lm, dFtrial, ...);
+ *              every few rounds: qr_lmb_batched_running(lm, &count), until count == 0
+ *
+ * The state (qr_lmb_batched_view): section 8m's fields, then lo, hi (n each), peg (n ints: -1 held at lo, +1 held at hi, 0 free), alpha
+ * (the fraction of the search's step that was taken) and clipped (1: alpha < 1).
+ *   info: section 8m's words, and -2 from qr_lmb_batched_start_dev for a member whose bounds are no box (lo_j > hi_j, or a NaN) or whose
+ *         x0 lies outside the box: nothing else of the member is written, and it is skipped from then on.
+ *
+ * qr_lmb_batched_step_dev: four launches: peg, qr_geqp3_batched_dev's, qr_ormqr_batched_dev's, the step.  Per running member, x_new = x - p:
+ *   P. peg, on the unfactored J and f: g_j = sum_i J(i, j) f_i for the columns whose x_j is exactly on a bound (a fixed order of summation);
+ *      peg_j = -1 if x_j == lo_j and g_j > 0, +1 if x_j == hi_j and g_j < 0, else 0.  The held columns of dJ are overwritten with zeros; the
+ *      factorisation then runs unchanged.  A zero column has acnorm 0, so rules b to e of section 8m need no change: D_j = 1 at a first
+ *      step, the column is left out of gnorm (gnorm is the scaled projected gradient), and a member whose every column is held ends with
+ *      status 4.
+ *   S. the step, between rules f and g of section 8m: s = -p; s_j = 0 exactly for every held j (*: rounding must not move a held variable
+ *      off its bound); s_j = 0 where x_j <= lo_j and s_j < 0, and where x_j >= hi_j and s_j > 0; alpha = min(1, the smallest
+ *      (bound_j - x_j) / s_j over the j with s_j != 0 whose x_j + s_j leaves the box); p~ = -alpha s; xtrial_j = x_j - p~_j clamped to
+ *      [lo_j, hi_j], and the bound itself, bitwise, for every j whose ratio equals alpha.  If nothing was zeroed and alpha == 1, rules g, h
+ *      and i hold verbatim.  Otherwise, with g_k the gradient entries of rule d: temp1 = |R P^T p~| / fnorm, prered = max(0, 2 sum_k p~_k g_k
+ *      / fnorm - temp1^2), dirder = -sum_k p~_k g_k / fnorm: the linear model's own reduction for the step taken.  pnorm stays the search's
+ *      |D p| in every case (*: with the truncated length the update's delta = pnorm / 0.5 collapses the radius onto the bound).
+ * qr_lmb_batched_update_dev: section 8m's update; while clipped is set the two tests on the reductions (status 1 and 6) are left out: a tiny
+ * alpha makes actred and prered tiny without meaning convergence.
+ *
+ * A variable that is free on its bound and whose step points outward is zeroed; if the trial is then rejected, the shrinking radius turns
+ * p towards -D^-2 g, which by rule P points inward for that variable: no list of banned variables is kept.
+ *
+ * Out of scope: the step from factors that already exist (section 8m's qr_lm_step_batched_dev has no bounded twin: the peg reads the
+ * unfactored J); general linear constraints on x; m < n.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct qr_lmb_batched qr_lmb_batched;
+
+typedef struct {
+    double *x, *xtrial, *D, *delta, *par, *fnorm, *xnorm, *pnorm, *gnorm, *prered, *dirder;
+    int *iter, *nfev, *njev, *accepted, *status, *info, *par_status;
+    double *lo, *hi, *alpha;
+    int *peg, *clipped;
+} qr_lmb_batched_state;
+
+/* the options and the shape rules are qr_lm_batched_create's */
+int qr_lmb_batched_create(qr_lmb_batched** lm, qr_plan* plan, int m, int n, int batch, const qr_lm_options* opt);
+/* dX0 and dD0 as in qr_lm_batched_start_dev; dLo, dHi: n per member (stride 0: one vector shared by all members, else >= n); either may
+ * be NULL: that side is unbounded */
+int qr_lmb_batched_start_dev(qr_lmb_batched* lm, const double* dX0, int ldx, long long strideX, const double* dD0, long long strideD,
+                             const double* dLo, long long strideLo, const double* dHi, long long strideHi);
+/* dJ: m x n (ldj >= m, strideJ >= ldj * n), dF: m per member (ldf >= m, strideF >= ldf).  dJ returns as geqp3 leaves it (the held columns
+ * factored as zeros), dF as Q^T f */
+int qr_lmb_batched_step_dev(qr_lmb_batched* lm, double* dJ, int ldj, long long strideJ, double* dF, int ldf, long long strideF);
+int qr_lmb_batched_update_dev(qr_lmb_batched* lm, const double* dFtrial, int ldf, long long strideF);
+int qr_lmb_batched_view(qr_lmb_batched* lm, qr_lmb_batched_state* state);
+/* count <- the members with status == 0 and info == 0.  The one call that waits on the host. */
+int qr_lmb_batched_running(qr_lmb_batched* lm, int* count);
+int qr_lmb_batched_destroy(qr_lmb_batched* lm);
+
+/* The whole solve of a packed batch on host pointers, as qr_lstsq_lm_batched: lo, hi (batch x n; either may be NULL: unbounded).  The X of
+ * a member with info -2 returns as it came.  Returns QR_E_SINGULAR if any info word is non-zero.  Creates a plan of its own.  Synchronous. */
+int qr_lstsq_lm_bounded_batched(qr_lm_fcn fcn, void* user, int m, int n, int batch, double* X, const double* lo, const double* hi,
+                                const double* D, const qr_lm_options* opt, double* fnorm, int* nfev, int* njev, int* status, int* info);
+
 #ifdef __cplusplus
 }
 #endif
