@@ -9,6 +9,8 @@
 #ifndef QR_BATCHED_DEV_H
 #define QR_BATCHED_DEV_H
 
+#include <float.h>
+
 #include <atomic>
 
 #include "qr_common.h"
@@ -42,12 +44,47 @@ __device__ __forceinline__ double qb_bcast(double v, int l)
 // the smallest leading dimension >= m that is 2 mod 32 (conflict-free column-major LDS image, see qr_update.hip)
 __host__ __device__ constexpr int qb_ld(int m) { return ((m + 29) / 32) * 32 + 2; }
 
-// LAPACK dlarfg's scalars from alpha and ssq = |x|^2 != 0: returns tau; v = x * scal
-__device__ __forceinline__ double qb_larfg(double alpha, double ssq, double& beta, double& scal)
+// LAPACK dlarfg's scalars from alpha and xnorm = |x| != 0: returns tau; v = x * scal
+__device__ __forceinline__ double qb_larfg_n(double alpha, double xnorm, double& beta, double& scal)
 {
-    beta = -copysign(hypot(alpha, sqrt(ssq)), alpha);
+    beta = -copysign(hypot(alpha, xnorm), alpha);
     scal = 1.0 / (alpha - beta);
     return (beta - alpha) / beta;
+}
+
+// .. from alpha and ssq = |x|^2 != 0
+__device__ __forceinline__ double qb_larfg(double alpha, double ssq, double& beta, double& scal)
+{
+    return qb_larfg_n(alpha, sqrt(ssq), beta, scal);
+}
+
+// The norm of a column from the plain sum of its squares.  A column of the data's own size squares into the double range wherever the
+// data is inside 1e+-150, but a column that cancellation has left at rounding size (a dependent column behind the pivots) lies sixteen
+// digits below the data, and from data of about 1e-145 its squares are subnormal: the sum keeps a few bits, and beta and tau belong to no
+// reflector.  While the plain sum lies inside QB_SSQ_LO .. QB_SSQ_HI its square root is the norm, bit for bit what the step always formed
+// (a term that went subnormal is then below 2^-100 of the sum).  Outside it the column is scaled by the power of two that brings its
+// largest entry into [1, 2) and summed again in the same order -- exact, so wherever no term of the plain sum overflows or goes subnormal
+// the result keeps the plain sum's bits as well.  A largest entry that is 0 or no finite number takes the plain sum.
+#define QB_SSQ_LO 0x1p-900
+#define QB_SSQ_HI 0x1p+900
+__device__ __forceinline__ bool qb_ssq_plain(double ssq) { return ssq >= QB_SSQ_LO && ssq <= QB_SSQ_HI; }
+
+__device__ __forceinline__ double qb_wave_max(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+// one wave, lane i holding x_i (0 in the lanes that hold none) and every lane ssq = qb_wave_sum(x * x): |x|, the same word in every lane
+__device__ __forceinline__ double qb_wave_nrm(double x, double ssq)
+{
+    if (qb_ssq_plain(ssq)) return sqrt(ssq);
+    const double xmax = qb_wave_max(fabs(x));
+    if (xmax == 0.0 || !(xmax <= DBL_MAX)) return sqrt(ssq);
+    const int e = ilogb(xmax);
+    const double xs = ldexp(x, -e);
+    return ldexp(sqrt(qb_wave_sum(xs * xs)), e);
 }
 
 // Wave route, step j (wave-uniform, j < the columns factored): lane i holds row i of the member in a[], rows past the last hold zeros.
@@ -58,12 +95,12 @@ template <int W>
 __device__ __forceinline__ void qb_wave_col(double (&a)[W], int j, int cend, int lane, double& tauv, double& diag)
 {
     const double x = lane > j ? a[j] : 0.0;
-    const double ssq = qb_wave_sum(x * x);
+    const double xnorm = qb_wave_nrm(x, qb_wave_sum(x * x));
     const double alpha = __shfl(a[j], j);
     double tj = 0.0;
-    if (ssq != 0.0) {
+    if (xnorm != 0.0) {
         double beta, scal;
-        tj = qb_larfg(alpha, ssq, beta, scal);
+        tj = qb_larfg_n(alpha, xnorm, beta, scal);
         const double v = lane > j ? a[j] * scal : (lane == j ? 1.0 : 0.0);
 #pragma unroll
         for (int c = j + 1; c < W; ++c) {
@@ -102,11 +139,34 @@ __device__ __forceinline__ double qb_wg_col(double* As, int ld, int m, int j, in
     if (lane == 0) red[wv] = s;
     __syncthreads();
     const double ssq = ((red[0] + red[1]) + red[2]) + red[3];
+    double xnorm = sqrt(ssq);
+    if (!qb_ssq_plain(ssq)) {                 // (the same value in every thread: the barriers below are met by all or by none)
+        double xmax = 0.0;
+        for (int i = j + 1 + t; i < m; i += 256) xmax = fmax(xmax, fabs(vj[i]));
+        xmax = qb_wave_max(xmax);
+        __syncthreads();                      // (every thread has read the four partial sums)
+        if (lane == 0) red[wv] = xmax;
+        __syncthreads();
+        xmax = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+        if (xmax != 0.0 && xmax <= DBL_MAX) {
+            const int e = ilogb(xmax);
+            s = 0.0;
+            for (int i = j + 1 + t; i < m; i += 256) {
+                const double xs = ldexp(vj[i], -e);
+                s = fma(xs, xs, s);
+            }
+            s = qb_wave_sum(s);
+            __syncthreads();                  // (every thread has read the four maxima)
+            if (lane == 0) red[wv] = s;
+            __syncthreads();
+            xnorm = ldexp(sqrt(((red[0] + red[1]) + red[2]) + red[3]), e);
+        }
+    }
     double tj = 0.0;
-    if (ssq != 0.0) {                         // (the same value in every thread)
+    if (xnorm != 0.0) {                       // (the same value in every thread)
         const double alpha = vj[j];
         double beta, scal;
-        tj = qb_larfg(alpha, ssq, beta, scal);
+        tj = qb_larfg_n(alpha, xnorm, beta, scal);
         __syncthreads();                      // (every thread has read alpha and the column)
         for (int i = j + 1 + t; i < m; i += 256) vj[i] *= scal;
         if (t == 0) vj[j] = beta;

@@ -48,12 +48,12 @@ __device__ __forceinline__ void bs_house(double* Gs, int ld, int n, int r, doubl
     const bool in = lane < n;
     for (int j = 0; j < r; ++j) {
         const double x = in && lane > j ? Gs[j * ld + lane] : 0.0;
-        const double ssq = qb_wave_sum(x * x);
+        const double xnorm = qb_wave_nrm(x, qb_wave_sum(x * x));
         const double alpha = Gs[j * ld + j];
         double tj = 0.0;
-        if (ssq != 0.0) {                     // (wave-uniform)
+        if (xnorm != 0.0) {                   // (wave-uniform)
             double beta, scal;                // (beta is not stored: only the trailing columns of this Q are used)
-            tj = qb_larfg(alpha, ssq, beta, scal);
+            tj = qb_larfg_n(alpha, xnorm, beta, scal);
             const double v = lane > j ? x * scal : (lane == j ? 1.0 : 0.0);
             for (int c = j + 1; c < r; ++c) {
                 const double y = in && lane >= j ? Gs[c * ld + lane] : 0.0;

@@ -58,6 +58,24 @@ __device__ __forceinline__ void bt_update(bt_state& S, double wnorm, double delt
     S.par = fmax(S.parl, S.par + parc);
 }
 
+// |g| of the scaled gradient, lane j holding g_j = (R^T z)_j / d_j (0 in lanes >= n): a product of two data quantities, whose square
+// leaves the double range where g itself is far inside it (MINPACK's enorm).  The largest |g_j| by a butterfly (the same word in every
+// lane, and in every wave that reads the same g); inside BT_G_LO .. BT_G_HI the plain sum, bit for bit what the search always formed.
+// Outside it g is scaled by the power of two that brings the largest entry into [1, 2) -- exact, so wherever no term of the plain sum
+// overflows or goes subnormal the result keeps the plain sum's bits as well.  A largest entry that is no finite number takes the plain sum.
+#define BT_G_LO 0x1p-256
+#define BT_G_HI 0x1p+256
+__device__ __forceinline__ double bt_wave_gnorm(double gl)
+{
+    double gmax = fabs(gl);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gmax = fmax(gmax, __shfl_xor(gmax, o));
+    if (gmax == 0.0 || (gmax >= BT_G_LO && gmax <= BT_G_HI) || !(gmax <= DBL_MAX)) return sqrt(qb_wave_sum(gl * gl));
+    const int e = ilogb(gmax);
+    const double gs = ldexp(gl, -e);
+    return ldexp(sqrt(qb_wave_sum(gs * gs)), e);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // wave route.  r[]: lane i < n holds row i of the master [R | z] (z in column n), zeros below the diagonal and in lanes >= n.  Rs: this
 // wave's image of the triangle (W x (W + 1) doubles); Xs: x, then W + 1 doubles on, the vector of the forward substitution.
@@ -141,7 +159,7 @@ __device__ __forceinline__ double bt_wave_core(const double (&r)[W], int n, int 
             }
         }
         gl = (lane < n && dsc != 0.0) ? gl / dsc : 0.0;
-        const double gnorm = sqrt(qb_wave_sum(gl * gl));
+        const double gnorm = bt_wave_gnorm(gl);
         bt_start(S, nsing == n, wnorm, gnorm, dxnorm, delta, par0);
         for (it = 1;; ++it) {
             if (S.par == 0.0) S.par = fmax(DBL_MIN, 0.001 * S.paru);
@@ -254,7 +272,7 @@ __device__ __forceinline__ void bt_wg_core(const double* Ms, double* Ws, double*
         }
         __syncthreads();
         const double gl = lane < n ? us[lane] : 0.0;
-        const double gnorm = sqrt(qb_wave_sum(gl * gl));
+        const double gnorm = bt_wave_gnorm(gl);
         bt_start(S, nsing == n, wnorm, gnorm, dxnorm, delta, par0);
         for (it = 1;; ++it) {
             if (S.par == 0.0) S.par = fmax(DBL_MIN, 0.001 * S.paru);

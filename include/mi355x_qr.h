@@ -1058,6 +1058,12 @@ int qr_lstsq_damped_batched(const double* A, int m, int n, const double* B, int 
  *      R~^T w = D^2 x / |D x|, parc = fp / (Delta |w|^2); fp > 0 raises parl to par, fp < 0 lowers paru to par; par = max(parl, par + parc).
  * MINPACK's constants are rtol = 0.1 and maxit = 10; here 0 < rtol < 1 and maxit >= 1 are arguments.
  *
+ * Range.  The search is good for factors, right-hand sides and radii whose entries, together with the products of one entry of R and
+ * one of z, lie inside 2^+-1000 (about 1e+-301): |g| is formed as MINPACK's enorm forms it, with the entries scaled by a power of two
+ * where their squares would leave the double range (the plain sum, bit for bit, while the largest |g_j| lies inside 2^+-256), so that
+ * g -- a product of two data quantities -- may be as large or small as its own value allows.  |D x| and |w| are plain sums of squares of
+ * quantities of the data's own size: good inside 1e+-150, the range of the library's other norms.
+ *
  * Section 8's conventions hold as in 8f, and jpvt, dD, flip, drss and the stride rules are exactly qr_damped_batched_dev's.  ddelta and
  * dlam0 (the starting guess for lambda; may be NULL: 0) hold one double per member; a stride of 0 means shared, any other must be >= 1.
  *

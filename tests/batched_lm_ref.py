@@ -61,7 +61,7 @@ def search(R, z, delta, d, jpvt, par0, rtol, maxit, dtype=np.float64):
         w = nrm(H.solve_rt(R0, dd * ((dd * x) / dxnorm), dtype))
         parl = ((fp / delta) / w) / w
     g = np.array([(R0[:j + 1, j] * z0[:j + 1]).sum() / dd[j] if dd[j] != 0 else 0 * dd[j] for j in range(n)])
-    gnorm = nrm(H.arr(g, dtype))
+    gnorm = T.gradient_norm(g, dtype)
     paru = gnorm / delta
     if paru == 0:
         paru = H.arr(TINY, dtype) / min(delta, H.arr(0.1, dtype))

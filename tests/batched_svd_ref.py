@@ -16,6 +16,8 @@ agree to rounding, sweep counts to the odd borderline pair.
 """
 import numpy as np
 
+import hp_ref as H
+
 EPS = np.finfo(np.float64).eps
 MAX_SWEEPS = 30                           # QR_JSVD_MAX_SWEEPS
 
@@ -114,9 +116,12 @@ def dlaqp2(A):
             vn1[p], vn2[p] = vn1[j], vn2[j]
         x = F[j + 1:, j]
         ssq = float(x @ x)
-        if ssq != 0.0:
+        e = H.column_scale(x, ssq)              # (the column step's guard: a rounding-sized column of tiny data is scaled before it is squared)
+        xs = np.ldexp(x, -e)
+        xnorm = float(np.ldexp(np.sqrt(float(xs @ xs)), e)) if e else np.sqrt(ssq)
+        if xnorm != 0.0:
             alpha = F[j, j]
-            beta = -np.copysign(np.hypot(alpha, np.sqrt(ssq)), alpha)
+            beta = -np.copysign(np.hypot(alpha, xnorm), alpha)
             tau[j] = (beta - alpha) / beta
             v = np.concatenate(([1.0], x / (alpha - beta)))
             F[j:, j + 1:] -= tau[j] * np.outer(v, v @ F[j:, j + 1:])

@@ -61,6 +61,22 @@ def gauss_newton_dxnorm(R, z, d=None, jpvt=None):
     return float(np.linalg.norm(dd * np.linalg.solve(np.triu(R), z)))
 
 
+G_WINDOW = 256
+
+
+def gradient_norm(g, dtype=np.float64):
+    """|g| as bt_wave_gnorm of qr_batched_trust_dev.h forms it: the plain sum of squares while the largest |g_j| lies within
+    2^-+G_WINDOW (or is 0, or no finite number); outside it g is first scaled by the power of two that brings that entry into [1, 2)"""
+    g = H.arr(g, dtype)
+    gmax = abs(g).max() if g.size else 0.0
+    lo, hi = np.ldexp(1.0, -G_WINDOW), np.ldexp(1.0, G_WINDOW)
+    if gmax == 0 or lo <= gmax <= hi or not np.isfinite(float(gmax)):
+        return H._root((g * g).sum(), dtype)
+    e = int(np.frexp(gmax)[1]) - 1
+    gs = np.ldexp(g, -e)
+    return np.ldexp(H._root((gs * gs).sum(), dtype), e)
+
+
 def lmpar(R, z, delta, d=None, jpvt=None, rss=None, flip=False, lam0=0.0, rtol=0.1, maxit=MAXIT, dtype=np.float64):
     """one member from factors: dict(X, lam, xnorm, resid, iter, status, info).  info != 0: the rest is None"""
     fail = lambda info: dict(X=None, lam=None, xnorm=None, resid=None, iter=None, status=None, info=info)
@@ -102,7 +118,7 @@ def lmpar(R, z, delta, d=None, jpvt=None, rss=None, flip=False, lam0=0.0, rtol=0
         w = nrm(H.solve_rt(R0, dd * ((dd * x) / dxnorm), dtype))
         parl = ((fp / delta) / w) / w
     g = np.array([(R0[:j + 1, j] * z0[:j + 1]).sum() / dd[j] if dd[j] != 0 else 0 * dd[j] for j in range(n)])
-    gnorm = nrm(H.arr(g, dtype))
+    gnorm = gradient_norm(g, dtype)
     paru = gnorm / delta
     if paru == 0:
         paru = H.arr(TINY, dtype) / min(delta, H.arr(0.1, dtype))

@@ -14,6 +14,7 @@ import numpy as np
 import hp_ref as H
 
 LD = H.LD
+EPS = H.EPS
 
 
 def _hypot(a, b, dtype):
@@ -99,3 +100,19 @@ class Accumulator:
         self.R, self.Z, self.rss = R, Z, np.where(rss > 0, rss, rss * 0)
         self.rows += p_add - p_del
         return 0
+
+
+def measures(n, p_add, m, Rn, C1n, C2n, Rld):
+    """the three ratios to their bounds for one member's results"""
+    p = m["B"].shape[0]
+    S = np.where(np.arange(p) < p_add, 1.0, -1.0)[:, None]
+    G0 = m["R"].T @ m["R"]
+    g = np.linalg.norm(Rn.T @ Rn - (G0 + m["B"].T @ (S * m["B"]))) / np.linalg.norm(G0) / (n * EPS)
+    kappa = np.linalg.cond(Rn)
+    e = float(H.norm(H.arr(Rn) - Rld) / H.norm(Rld)) / (50 * kappa * EPS)
+    inv = 0.0
+    if m["C1"].shape[1]:
+        before = (m["C1"] ** 2).sum(axis=0) + (S * m["C2"] ** 2).sum(axis=0)
+        after = (C1n ** 2).sum(axis=0) + (S * C2n ** 2).sum(axis=0)
+        inv = np.max(np.abs(after - before) / ((m["C1"] ** 2).sum(axis=0) + (m["C2"] ** 2).sum(axis=0))) / ((n + p) * EPS)
+    return g, e, inv

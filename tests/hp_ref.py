@@ -43,13 +43,40 @@ def norm(x, dtype=LD):
     return _root((x * x).sum(), dtype)
 
 
+SSQ_WINDOW = 900
+
+
+def ssq_is_plain(ssq):
+    """qb_ssq_plain of csrc/qr_batched_dev.h: the plain sum of squares lies within 2^-+SSQ_WINDOW, so its square root is the norm"""
+    return np.ldexp(1.0, -SSQ_WINDOW) <= ssq <= np.ldexp(1.0, SSQ_WINDOW)
+
+
+def column_scale(x, ssq):
+    """the exponent e by which the float64 column x, of plain sum of squares ssq, is scaled before it is squared (x 2^-e), as the
+    Householder column step of the batched kernels does (qb_wave_nrm, qb_wg_col of csrc/qr_batched_dev.h): 0 while ssq lies inside the
+    window, or where the largest |x_i| is 0 or no finite number; else the exponent that brings the largest |x_i| into [1, 2)"""
+    if ssq_is_plain(ssq):
+        return 0
+    xmax = float(np.max(np.abs(x), initial=0.0))
+    if xmax == 0 or not np.isfinite(xmax):
+        return 0
+    return int(np.frexp(xmax)[1]) - 1
+
+
 def _house(x, dtype):
-    """dlarfg on x (modified in place: x[0] <- beta, x[1:] <- v's tail); returns tau"""
+    """dlarfg on x (modified in place: x[0] <- beta, x[1:] <- v's tail); returns tau.  In float64 a tail whose plain sum of squares
+    leaves 2^-+SSQ_WINDOW is scaled by a power of two first (column_scale): exact, so the homogeneity holds bit for bit as before
+    wherever no square leaves the normal range, and a rounding-sized column of data near 1e-145 keeps a reflector that is one"""
     alpha = x[0]
     ssq = (x[1:] * x[1:]).sum() if x.size > 1 else 0
-    if ssq == 0:
+    if ssq == 0 and not (dtype is np.float64 and x.size > 1 and np.any(x[1:] != 0)):
         return alpha * 0
-    nrm = _root(alpha * alpha + ssq, dtype)
+    e = column_scale(x[1:], ssq) if dtype is np.float64 else 0
+    if e:
+        xs, al = np.ldexp(x[1:], -e), np.ldexp(alpha, -e)
+        nrm = np.ldexp(_root(al * al + (xs * xs).sum(), dtype), e)
+    else:
+        nrm = _root(alpha * alpha + ssq, dtype)
     beta = -nrm if alpha >= 0 else nrm
     x[1:] = x[1:] / (alpha - beta)
     x[0] = beta

@@ -69,20 +69,7 @@ def _draw(rng, n, nrhs, p_add, p_del):
                 A=np.vstack([rows[mask], new]), Y=np.vstack([y[mask], ynew]))
 
 
-def _measures(n, p_add, m, Rn, C1n, C2n, Rld):
-    """the three ratios to their bounds for one member's results"""
-    p = m["B"].shape[0]
-    S = np.where(np.arange(p) < p_add, 1.0, -1.0)[:, None]
-    G0 = m["R"].T @ m["R"]
-    g = np.linalg.norm(Rn.T @ Rn - (G0 + m["B"].T @ (S * m["B"]))) / np.linalg.norm(G0) / (n * EPS)
-    kappa = np.linalg.cond(Rn)
-    e = float(H.norm(H.arr(Rn) - Rld) / H.norm(Rld)) / (50 * kappa * EPS)
-    inv = 0.0
-    if m["C1"].shape[1]:
-        before = (m["C1"] ** 2).sum(axis=0) + (S * m["C2"] ** 2).sum(axis=0)
-        after = (C1n ** 2).sum(axis=0) + (S * C2n ** 2).sum(axis=0)
-        inv = np.max(np.abs(after - before) / ((m["C1"] ** 2).sum(axis=0) + (m["C2"] ** 2).sum(axis=0))) / ((n + p) * EPS)
-    return g, e, inv
+_measures = U.measures              # the three ratios to their bounds for one member's results
 
 
 @functools.lru_cache(maxsize=None)

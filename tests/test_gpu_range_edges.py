@@ -402,23 +402,27 @@ def _edge_section7_gesvj(qr, plan, s):
 
 
 def _edge_section8_batched(qr, plan, s):
-    m = n = 17
-    A = _input("batched", lambda: U(8117, 3, m, n))
-    Bm = U(8118, 3, m, 2)
-    F, tau, _ = tb._factor(plan, s * A, with_q=False)
-    X, rss, info = tb._gels(plan, s * A, Bm)
-    Fp, taup, jp, _ = tbp._geqp3(plan, s * A, with_q=False)
-    Xy, resid, rank, jp2, _, _, _ = tbp._solve(plan, s * A, Bm, True)
-    _same_status("batched", s, np.concatenate([info, rank, jp.ravel(), jp2.ravel()]))
-    assert not info.any() and np.all(rank == n) and np.isfinite(X).all() and np.isfinite(Xy).all() and np.isfinite(resid).all()
-    for k in range(3):
-        _input(("batched", k), lambda: A[k].copy())
-        _check_factor(f"geqrf_batched 17x17 [{k}]", ("batched", k), s, F[k], tau[k], caps=((n + 8) * EPS, (n + 8) * EPS))
-        _check_factor(f"geqp3_batched 17x17 [{k}]", ("batched", k), s, Fp[k], taup[k], jp[k], caps=((n + 8) * EPS, (n + 8) * EPS))
-        Xr, _ = H.lstsq(A[k], Bm[k], np.float64)
-        rne = H.normal_equations_residual(A[k], Xr, Bm[k])
-        _within(f"gels_batched 17x17 [{k}] normal equations", H.normal_equations_residual(s * A[k], X[k], Bm[k]), rne)
-        _within(f"gelsy_batched 17x17 [{k}] normal equations", H.normal_equations_residual(s * A[k], Xy[k], Bm[k]), rne)
+    """17 x 17 (the wave route) and 100 x 33 (the workgroup route of the unpivoted and of the bp_* kernels)"""
+    for m, n in ((17, 17), (100, 33)):
+        key = "batched" if m == 17 else ("batched", m, n)
+        A = _input(key, lambda: U(8117 + (m != 17) * (m + n), 3, m, n))
+        Bm = U(8118 + (m != 17) * (m + n), 3, m, 2)
+        F, tau, _ = tb._factor(plan, s * A, with_q=False)
+        X, rss, info = tb._gels(plan, s * A, Bm)
+        Fp, taup, jp, _ = tbp._geqp3(plan, s * A, with_q=False)
+        Xy, resid, rank, jp2, _, _, _ = tbp._solve(plan, s * A, Bm, True)
+        _same_status(key, s, np.concatenate([info, rank, jp.ravel(), jp2.ravel()]))
+        assert not info.any() and np.all(rank == n) and np.isfinite(X).all() and np.isfinite(Xy).all() and np.isfinite(resid).all()
+        assert np.isfinite(rss).all()
+        for k in range(3):
+            ck = ("batched", k) if m == 17 else ("batched", m, n, k)
+            _input(ck, lambda: A[k].copy())
+            _check_factor(f"geqrf_batched {m}x{n} [{k}]", ck, s, F[k], tau[k], caps=((n + 8) * EPS, (n + 8) * EPS))
+            _check_factor(f"geqp3_batched {m}x{n} [{k}]", ck, s, Fp[k], taup[k], jp[k], caps=((n + 8) * EPS, (n + 8) * EPS))
+            Xr, _ = H.lstsq(A[k], Bm[k], np.float64)
+            rne = H.normal_equations_residual(A[k], Xr, Bm[k])
+            _within(f"gels_batched {m}x{n} [{k}] normal equations", H.normal_equations_residual(s * A[k], X[k], Bm[k]), rne)
+            _within(f"gelsy_batched {m}x{n} [{k}] normal equations", H.normal_equations_residual(s * A[k], Xy[k], Bm[k]), rne)
 
 
 EDGE_CASES = {f.__name__[6:]: f for f in (_edge_guarded_leaf_panel, _edge_one_launch_panel, _edge_full_width_panel, _edge_geqrf,
