@@ -1907,18 +1907,24 @@ class LmBatched:
     is the one call that waits on the host.  The calls run on the plan's stream: model code in torch runs there too inside
     `with torch.cuda.stream(torch.cuda.ExternalStream(plan.stream))`.  The plan must stay open for as long as the solver is used."""
     _state = LmState
+    _prefix = "qr_lm_batched"          # the C calls are _prefix + "_create", "_start_dev", ..: a subclass names another family
+
+    def _call(self, suffix, *args):
+        name = self._prefix + suffix
+        check(getattr(lib, name)(self.h, *args), name)
 
     def __init__(self, plan, m, n, batch, **options):
         self.h = None
         self.options = lm_options(**options)
         h = _vp()
-        check(lib.qr_lm_batched_create(C.byref(h), plan.h, m, n, batch, C.byref(self.options)), "qr_lm_batched_create")
+        name = self._prefix + "_create"
+        check(getattr(lib, name)(C.byref(h), plan.h, m, n, batch, C.byref(self.options)), name)
         self.h, self.plan, self.m, self.n, self.batch = h, plan, m, n, batch
         self._views = None
 
     def close(self):
         if self.h and lib is not None and self.plan.h:
-            lib.qr_lm_batched_destroy(self.h)
+            getattr(lib, self._prefix + "_destroy")(self.h)
         self.h = None
 
     __del__ = close
@@ -1926,26 +1932,25 @@ class LmBatched:
     def start(self, dX0, ldx=None, strideX=None, dD0=None, strideD=None):
         """x <- dX0 (n per member, packed unless ldx / strideX say otherwise); dD0: the scaling of mode 2 (strideD 0: shared)"""
         ldx = self.n if ldx is None else ldx
-        check(lib.qr_lm_batched_start_dev(self.h, _dptr(dX0), ldx, ldx if strideX is None else strideX, _dptr(dD0),
-                                          self.n if strideD is None else strideD), "qr_lm_batched_start_dev")
+        self._call("_start_dev", _dptr(dX0), ldx, ldx if strideX is None else strideX, _dptr(dD0), self.n if strideD is None else strideD)
 
     def step(self, dJ, dF, ldj=None, strideJ=None, ldf=None, strideF=None):
-        """dJ (m x n per member, column-major) <- its pivoted factors, dF (m per member) <- Q^T f, then the step of every running member"""
+        """dJ (m x n per member, column-major) <- its pivoted factors, dF (m per member) <- Q^T f, then the step of every running member
+        (LmBoundedBatched: the peg on dJ and dF in front, and the step cut to the box)"""
         ldj = self.m if ldj is None else ldj
         ldf = self.m if ldf is None else ldf
-        check(lib.qr_lm_batched_step_dev(self.h, _dptr(dJ), ldj, ldj * self.n if strideJ is None else strideJ, _dptr(dF), ldf,
-                                         ldf if strideF is None else strideF), "qr_lm_batched_step_dev")
+        self._call("_step_dev", _dptr(dJ), ldj, ldj * self.n if strideJ is None else strideJ, _dptr(dF), ldf, ldf if strideF is None else strideF)
 
     def update(self, dFtrial, ldf=None, strideF=None):
         """dFtrial (m per member): f at the trial points"""
         ldf = self.m if ldf is None else ldf
-        check(lib.qr_lm_batched_update_dev(self.h, _dptr(dFtrial), ldf, ldf if strideF is None else strideF), "qr_lm_batched_update_dev")
+        self._call("_update_dev", _dptr(dFtrial), ldf, ldf if strideF is None else strideF)
 
     def view(self):
         """the device addresses of the state: a dict of ints"""
-        v = LmState()
-        check(lib.qr_lm_batched_view(self.h, C.byref(v)), "qr_lm_batched_view")
-        return {k: getattr(v, k) for k, _ in LmState._fields_}
+        v = self._state()
+        self._call("_view", C.byref(v))
+        return {k: getattr(v, k) for k, _ in self._state._fields_}
 
     def state(self, device=None):
         """the state as zero-copy torch views: x, xtrial, D (batch, n) float64; delta, par, fnorm, xnorm, pnorm, gnorm, prered, dirder
@@ -1969,7 +1974,7 @@ class LmBatched:
     def running(self):
         """the number of members with status == 0 and info == 0; waits for the plan's stream"""
         c = C.c_int()
-        check(lib.qr_lm_batched_running(self.h, C.byref(c)), "qr_lm_batched_running")
+        self._call("_running", C.byref(c))
         return c.value
 
 
@@ -1978,50 +1983,14 @@ class LmBoundedBatched(LmBatched):
     start takes the bounds, and state() has lo, hi (batch, n) float64, peg (batch, n) int32, alpha (batch,) float64 and clipped (batch,)
     int32 as well."""
     _state = LmBoundedState
-
-    def __init__(self, plan, m, n, batch, **options):
-        self.h = None
-        self.options = lm_options(**options)
-        h = _vp()
-        check(lib.qr_lmb_batched_create(C.byref(h), plan.h, m, n, batch, C.byref(self.options)), "qr_lmb_batched_create")
-        self.h, self.plan, self.m, self.n, self.batch = h, plan, m, n, batch
-        self._views = None
-
-    def close(self):
-        if self.h and lib is not None and self.plan.h:
-            lib.qr_lmb_batched_destroy(self.h)
-        self.h = None
-
-    __del__ = close
+    _prefix = "qr_lmb_batched"
 
     def start(self, dX0, ldx=None, strideX=None, dD0=None, strideD=None, dLo=None, strideLo=None, dHi=None, strideHi=None):
         """x <- dX0, the scaling of mode 2 as in LmBatched.start; dLo, dHi: the bounds, n per member (stride 0: one vector shared by all
         members; None: that side is unbounded)"""
         ldx = self.n if ldx is None else ldx
-        check(lib.qr_lmb_batched_start_dev(self.h, _dptr(dX0), ldx, ldx if strideX is None else strideX, _dptr(dD0),
-                                           self.n if strideD is None else strideD, _dptr(dLo), self.n if strideLo is None else strideLo,
-                                           _dptr(dHi), self.n if strideHi is None else strideHi), "qr_lmb_batched_start_dev")
-
-    def step(self, dJ, dF, ldj=None, strideJ=None, ldf=None, strideF=None):
-        """the peg on dJ and dF, then LmBatched.step's three launches with the step cut to the box"""
-        ldj = self.m if ldj is None else ldj
-        ldf = self.m if ldf is None else ldf
-        check(lib.qr_lmb_batched_step_dev(self.h, _dptr(dJ), ldj, ldj * self.n if strideJ is None else strideJ, _dptr(dF), ldf,
-                                          ldf if strideF is None else strideF), "qr_lmb_batched_step_dev")
-
-    def update(self, dFtrial, ldf=None, strideF=None):
-        ldf = self.m if ldf is None else ldf
-        check(lib.qr_lmb_batched_update_dev(self.h, _dptr(dFtrial), ldf, ldf if strideF is None else strideF), "qr_lmb_batched_update_dev")
-
-    def view(self):
-        v = LmBoundedState()
-        check(lib.qr_lmb_batched_view(self.h, C.byref(v)), "qr_lmb_batched_view")
-        return {k: getattr(v, k) for k, _ in LmBoundedState._fields_}
-
-    def running(self):
-        c = C.c_int()
-        check(lib.qr_lmb_batched_running(self.h, C.byref(c)), "qr_lmb_batched_running")
-        return c.value
+        self._call("_start_dev", _dptr(dX0), ldx, ldx if strideX is None else strideX, _dptr(dD0), self.n if strideD is None else strideD,
+                   _dptr(dLo), self.n if strideLo is None else strideLo, _dptr(dHi), self.n if strideHi is None else strideHi)
 
 
 def _lm_bounds_dev(bounds, batch, n, device):

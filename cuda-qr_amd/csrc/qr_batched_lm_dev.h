@@ -1,7 +1,7 @@
-// qr_batched_lm_dev.h -- the rules of MINPACK lmder's outer loop that qr_batched_lm.hip (mi355x_qr.h section 8m) and qr_batched_lmb.hip
-// (section 8n, the same loop with box bounds on x) both run: the scalars of a step (rules c, d and e), the end of a step (rules g, h and
-// i), the refusal of a search, and the update.  No kernels, no entry points.  Both files run the code below, so the bounded solver with
-// every bound infinite returns the bits of section 8m.
+// qr_batched_lm_dev.h -- the rules of MINPACK lmder's outer loop that the kernels of qr_batched_lm.hip run for mi355x_qr.h section 8m and
+// for section 8n (the same loop with box bounds on x): the scalars of a step (rules c, d and e), the end of a step (rules g, h and i),
+// the refusal of a search, the update and the start.  No kernels, no entry points.  Both sections run the code below, so the bounded
+// solver with every bound infinite returns the bits of section 8m.
 //
 // Every sum runs in a fixed order; every scalar rule is compiled with contraction off, so that each rounding is the one written.
 #ifndef QR_BATCHED_LM_DEV_H

@@ -465,8 +465,8 @@ int qrd_blm_start(void* stream, const double* X0, int ldx, size_t sX, const doub
 int qrd_blm_step(void* stream, const qrd_blm_step_args* a);
 int qrd_blm_update(void* stream, const double* Ft, int m, int ldf, size_t sF, int n, int batch, const qrd_blm_state* s, const qrd_blm_opts* o);
 
-/* batched Levenberg-Marquardt with box bounds on x (qr_batched_lmb.hip, called from qr_batched_lmb.c only; mi355x_qr.h section 8n): the
- * loop above with MPFIT's rules for lo <= x <= hi.  The rules of section 8m are the device code of qr_batched_lm_dev.h in both files.
+/* batched Levenberg-Marquardt with box bounds on x (qr_batched_lm.hip, called from qr_batched_lm.c only; mi355x_qr.h section 8n): the
+ * loop above with MPFIT's rules for lo <= x <= hi.  The step kernels are section 8m's, instantiated on qrd_blmb_step_args.
  *   qrd_blmb_state: qrd_blm_state, then lo, hi (n per member), peg (n ints per member: -1 held at lo, +1 held at hi, 0 free), alpha (the
  *   fraction of the step taken) and clipped (alpha < 1), one each.
  *   qrd_blmb_start: qrd_blm_start, and lo <- Lo (sLo apart, 0: shared; NULL: -inf), hi <- Hi likewise (NULL: +inf).  A member whose

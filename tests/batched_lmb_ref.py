@@ -1,4 +1,4 @@
-"""A numpy restatement of the bounded batched Levenberg-Marquardt solver (mi355x_qr.h section 8n; kernels: csrc/qr_batched_lmb.hip) for one
+"""A numpy restatement of the bounded batched Levenberg-Marquardt solver (mi355x_qr.h section 8n; kernels: csrc/qr_batched_lm.hip) for one
 member, on top of batched_lm_ref.Member, with the bounded test problems (helper module, no fixtures, no GPU).
 
 BMember adds the three rules to Member: P (the peg, on the unfactored J and f, the sum in the kernel's order: lane l takes rows l,

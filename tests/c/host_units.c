@@ -1,4 +1,4 @@
-/* host_units.c -- TEST-ONLY driver of the seventeen per-interface host units (qr_solve.c ... qr_batched_lm.c) over the stub device layer
+/* host_units.c -- TEST-ONLY driver of the seventeen per-interface host units (qr_solve.c ... qr_batched_lm.c, which holds sections 8m and 8n) over the stub device layer
  * (qrd_stub.c, qrd_stub_units.c; tests/test_units_stub.py; DESIGN "Host units over the stub").  One named configuration per process, as
  * in host_order.c: `host_units list` prints the names, `host_units <name>` runs one, `host_units threads` runs four host threads on
  * different host-pointer twins (the ThreadSanitizer build).  Every caller-side device buffer is allocated at exactly the minimum size the
@@ -808,90 +808,160 @@ static int lm_model(void* user, int what, const double* X, int batch, double* F,
     ++calls[what];
     return calls[0] && calls[what] > calls[0] ? 77 : 0;          /* calls[0]: the call of this kind that fails (0: none) */
 }
-static void blm_on(const bshape* s)
+/* a handle of either section behind the calls the two share */
+typedef struct { int bounded; qr_lm_batched* u; qr_lmb_batched* b; } lm_any;
+static int any_create(lm_any* a, qr_plan* p, int m, int n, int batch, const qr_lm_options* o)
+{ return a->bounded ? qr_lmb_batched_create(&a->b, p, m, n, batch, o) : qr_lm_batched_create(&a->u, p, m, n, batch, o); }
+static int any_start(lm_any* a, const double* X0, int ldx, long long sX, const double* D0, long long sD)
+{ return a->bounded ? qr_lmb_batched_start_dev(a->b, X0, ldx, sX, D0, sD, NULL, 0, NULL, 0) : qr_lm_batched_start_dev(a->u, X0, ldx, sX, D0, sD); }
+static int any_step(lm_any* a, double* J, int ldj, long long sJ, double* F, int ldf, long long sF)
+{ return a->bounded ? qr_lmb_batched_step_dev(a->b, J, ldj, sJ, F, ldf, sF) : qr_lm_batched_step_dev(a->u, J, ldj, sJ, F, ldf, sF); }
+static int any_update(lm_any* a, const double* F, int ldf, long long sF)
+{ return a->bounded ? qr_lmb_batched_update_dev(a->b, F, ldf, sF) : qr_lm_batched_update_dev(a->u, F, ldf, sF); }
+static int any_running(lm_any* a, int* count) { return a->bounded ? qr_lmb_batched_running(a->b, count) : qr_lm_batched_running(a->u, count); }
+static int any_destroy(lm_any* a) { return a->bounded ? qr_lmb_batched_destroy(a->b) : qr_lm_batched_destroy(a->u); }
+static void blm_on(const bshape* s, int bounded)
 {
     qr_plan* p = NULL;
-    qr_lm_batched* h = NULL;
+    lm_any h = {bounded, NULL, NULL};
+    const char* upd = bounded ? "blmb_update" : "blm_update";
     CALL(qr_plan_create(&p, 64, 8, 0, 0));
     const int m = s->m, n = s->n, b = s->batch, ldj = LD(m), ldx = LD(n);
     const long long sJ = ST(ldj, n), sF = ST(ldj, 1), sX = ldx + s->gap, sn = n + s->gap;
-    double *J = DB(m, n), *F = DB(m, 1), *X0 = dev_blocks(n, 1, ldx, b, sX), *D0 = DV(n), *rss = PK(1);
+    double *J = DB(m, n), *F = DB(m, 1), *X0 = dev_blocks(n, 1, ldx, b, sX), *D0 = DV(n), *Lo = DV(n), *Hi = dev_vec(n), *rss = PK(1);
     int* jp = DI(n);
     qr_lm_options o;
     qr_lm_options_default(&o);
     for (int mode = 1; mode <= 2; ++mode) {
         o.mode = mode;
-        CALL(qr_lm_batched_create(&h, p, m, n, b, mode == 1 ? NULL : &o));
+        CALL(any_create(&h, p, m, n, b, mode == 1 ? NULL : &o));
         int count = -1;
-        ARG(qr_lm_batched_running(h, &count));
-        ARG(qr_lm_batched_step_dev(h, J, ldj, sJ, F, ldj, sF));      /* before start */
-        CALL(qr_lm_batched_start_dev(h, X0, ldx, sX, D0, mode == 2 ? 0 : sn));
-        CALL(qr_lm_batched_start_dev(h, X0, ldx, sX, mode == 2 ? D0 : NULL, sn));
-        CALL(qr_lm_batched_step_dev(h, J, ldj, sJ, F, ldj, sF));
-        ARG(qr_lm_batched_step_dev(h, J, ldj, sJ, F, ldj, sF));      /* a step behind a step */
+        ARG(any_running(&h, &count));
+        ARG(any_step(&h, J, ldj, sJ, F, ldj, sF));      /* before start */
+        CALL(any_start(&h, X0, ldx, sX, D0, mode == 2 ? 0 : sn));
+        CALL(any_start(&h, X0, ldx, sX, mode == 2 ? D0 : NULL, sn));
+        if (bounded) {          /* the bounds: per member, one vector shared by all (stride 0), one side or both absent */
+            CALL(qr_lmb_batched_start_dev(h.b, X0, ldx, sX, D0, sn, Lo, sn, Hi, 0));
+            CALL(qr_lmb_batched_start_dev(h.b, X0, ldx, sX, D0, sn, Hi, 0, Lo, sn));
+            CALL(qr_lmb_batched_start_dev(h.b, X0, ldx, sX, D0, sn, Lo, sn, NULL, -1));
+            CALL(qr_lmb_batched_start_dev(h.b, X0, ldx, sX, D0, sn, NULL, -1, Hi, 0));
+            ARG(qr_lmb_batched_start_dev(h.b, X0, ldx, sX, D0, sn, Lo, n - 1, Hi, 0));
+            ARG(qr_lmb_batched_start_dev(h.b, X0, ldx, sX, D0, sn, Lo, sn, Hi, -1));
+            /* a handle of section 8n is refused by every call of section 8m */
+            qr_lm_batched* wrong = (qr_lm_batched*) h.b;
+            qr_lm_batched_state wv;
+            ARG(qr_lm_batched_start_dev(wrong, X0, ldx, sX, D0, sn));
+            ARG(qr_lm_batched_step_dev(wrong, J, ldj, sJ, F, ldj, sF));
+            ARG(qr_lm_step_batched_dev(wrong, J, ldj, sJ, F, m, ldj, sF, rss, jp, sn));
+            ARG(qr_lm_batched_update_dev(wrong, F, ldj, sF));
+            ARG(qr_lm_batched_running(wrong, &count));
+            ARG(qr_lm_batched_view(wrong, &wv));
+            ARG(qr_lm_batched_destroy(wrong));
+        } else {                /* and the other way round */
+            qr_lmb_batched* wrong = (qr_lmb_batched*) h.u;
+            qr_lmb_batched_state wv;
+            ARG(qr_lmb_batched_start_dev(wrong, X0, ldx, sX, D0, sn, NULL, 0, NULL, 0));
+            ARG(qr_lmb_batched_step_dev(wrong, J, ldj, sJ, F, ldj, sF));
+            ARG(qr_lmb_batched_update_dev(wrong, F, ldj, sF));
+            ARG(qr_lmb_batched_running(wrong, &count));
+            ARG(qr_lmb_batched_view(wrong, &wv));
+            ARG(qr_lmb_batched_destroy(wrong));
+        }
+        CALL(any_step(&h, J, ldj, sJ, F, ldj, sF));
+        ARG(any_step(&h, J, ldj, sJ, F, ldj, sF));      /* a step behind a step */
         const double keep = b > 1 ? b - 1 : 1;
-        CALLS(qrd_stub_script("blm_update", &keep, 1), qr_lm_batched_update_dev(h, F, ldj, sF), 0);
-        CALL(qr_lm_batched_running(h, &count));
+        CALLS(qrd_stub_script(upd, &keep, 1), any_update(&h, F, ldj, sF), 0);
+        CALL(any_running(&h, &count));
         if (count != (int) keep) { fprintf(stderr, "running %d\n", count); exit(1); }
-        CALL(qr_lm_step_batched_dev(h, J, ldj, sJ, F, m, ldj, sF, rss, jp, sn));
-        ARG(qr_lm_batched_update_dev(h, F, m - 1, sF));
-        CALL(qr_lm_batched_update_dev(h, F, ldj, sF));
-        CALL(qr_lm_step_batched_dev(h, J, ldj, sJ, F, n, ldj, sF, NULL, NULL, 0));
-        CALL(qr_lm_batched_update_dev(h, F, ldj, sF));
-        CALL(qr_lm_batched_running(h, &count));
+        /* (the step from factors that exist is section 8m's alone) */
+        CALL(bounded ? any_step(&h, J, ldj, sJ, F, ldj, sF) : qr_lm_step_batched_dev(h.u, J, ldj, sJ, F, m, ldj, sF, rss, jp, sn));
+        ARG(any_update(&h, F, m - 1, sF));
+        CALL(any_update(&h, F, ldj, sF));
+        CALL(bounded ? any_step(&h, J, ldj, sJ, F, ldj, sF) : qr_lm_step_batched_dev(h.u, J, ldj, sJ, F, n, ldj, sF, NULL, NULL, 0));
+        CALL(any_update(&h, F, ldj, sF));
+        CALL(any_running(&h, &count));
         if (count != 0) { fprintf(stderr, "running %d after the last update\n", count); exit(1); }
-        qr_lm_batched_state v;
-        CALL(qr_lm_batched_view(h, &v));
-        ARG(qr_lm_step_batched_dev(h, J, n - 1, sJ, F, m, ldj, sF, rss, jp, sn));
-        ARG(qr_lm_batched_start_dev(h, X0, n - 1, sX, D0, sn));
-        CALL(qr_lm_batched_destroy(h));
+        if (bounded) {
+            qr_lmb_batched_state v;
+            CALL(qr_lmb_batched_view(h.b, &v));
+            if (!v.lo || !v.hi || !v.alpha || !v.peg || !v.clipped) { fprintf(stderr, "the view of a bounded handle lacks the bounds\n"); exit(1); }
+        } else {
+            qr_lm_batched_state v;
+            CALL(qr_lm_batched_view(h.u, &v));
+            ARG(qr_lm_step_batched_dev(h.u, J, n - 1, sJ, F, m, ldj, sF, rss, jp, sn));
+        }
+        ARG(any_start(&h, X0, n - 1, sX, D0, sn));
+        CALL(any_destroy(&h));
     }
-    ARG(qr_lm_batched_create(&h, p, m, 64, b, NULL));
-    ARG(qr_lm_batched_create(&h, p, qr_batched_max_rows(n + 1) + 1, n, b, NULL));
+    ARG(any_create(&h, p, m, 64, b, NULL));
+    ARG(any_create(&h, p, qr_batched_max_rows(n + 1) + 1, n, b, NULL));
     o.par_rtol = 1.0;
-    ARG(qr_lm_batched_create(&h, p, m, n, b, &o));
-    CALL(qr_lm_batched_create(&h, p, m, n, 0, NULL));
-    CALL(qr_lm_batched_start_dev(h, X0, ldx, sX, NULL, 0));
-    CALL(qr_lm_batched_destroy(h));
+    ARG(any_create(&h, p, m, n, b, &o));
+    CALL(any_create(&h, p, m, n, 0, NULL));
+    CALL(any_start(&h, X0, ldx, sX, NULL, 0));
+    CALL(any_destroy(&h));
     CALL(qr_plan_sync(p));
     CALL(qr_plan_destroy(p));
 }
-static void blm_wave(void) { const bshape s = {40, 7, 1, 5, 1, 3}; blm_on(&s); }
-static void blm_wave_edge(void) { const bshape s = {64, 31, 1, 1, 3, 0}; blm_on(&s); }
-static void blm_wg(void) { const bshape s = {256, 63, 1, 3, 1, 1}; blm_on(&s); }
-static void blm_twin(void)
+static void blm_wave(void) { const bshape s = {40, 7, 1, 5, 1, 3}; blm_on(&s, 0); }
+static void blm_wave_edge(void) { const bshape s = {64, 31, 1, 1, 3, 0}; blm_on(&s, 0); }
+static void blm_wg(void) { const bshape s = {256, 63, 1, 3, 1, 1}; blm_on(&s, 0); }
+static void blmb_wave(void) { const bshape s = {40, 7, 1, 5, 1, 3}; blm_on(&s, 1); }
+static void blmb_wave_edge(void) { const bshape s = {64, 31, 1, 1, 3, 0}; blm_on(&s, 1); }
+static void blmb_wg(void) { const bshape s = {256, 63, 1, 3, 1, 1}; blm_on(&s, 1); }
+/* the host-pointer twin of either section; lo, hi: section 8n's bounds (either may be NULL) */
+static int twin_solve(int bounded, int* calls, int m, int n, int b, double* X, const double* lo, const double* hi, const double* D,
+                      const qr_lm_options* o, double* fn, int* nfev, int* njev, int* st, int* info)
+{
+    return bounded ? qr_lstsq_lm_bounded_batched(lm_model, calls, m, n, b, X, lo, hi, D, o, fn, nfev, njev, st, info)
+                   : qr_lstsq_lm_batched(lm_model, calls, m, n, b, X, D, o, fn, nfev, njev, st, info);
+}
+static void twin_on(int bounded)
 {
     const int m = 40, n = 7, b = 5;
-    double *X = hostd((size_t) n * b), *D = hostd((size_t) n * b), *fn = hostd(b);
+    const char* upd = bounded ? "blmb_update" : "blm_update";
+    double *X = hostd((size_t) n * b), *D = hostd((size_t) n * b), *fn = hostd(b), *lo = hostd((size_t) n * b), *hi = hostd((size_t) n * b);
     int *nfev = hosti(b), *njev = hosti(b), *st = hosti(b), *info = hosti(b), calls[4] = {0, 0, 0, 0};
     qr_lm_options o;
     qr_lm_options_default(&o);
-    CALL(qr_lstsq_lm_batched(lm_model, calls, m, n, b, X, NULL, NULL, fn, nfev, njev, st, info));          /* every member finishes in the first round */
+    CALL(twin_solve(bounded, calls, m, n, b, X, NULL, NULL, NULL, NULL, fn, nfev, njev, st, info));          /* every member finishes in the first round */
     /* four rounds: all running, one finished, a rejected step with two left, then the end */
     { const double w[4] = {5.0, 4.0, -2.0, 0.0}; memset(calls, 0, sizeof calls);
-      CALLS(qrd_stub_script("blm_update", w, 4), qr_lstsq_lm_batched(lm_model, calls, m, n, b, X, NULL, &o, NULL, NULL, NULL, NULL, info), 0);
+      CALLS(qrd_stub_script(upd, w, 4), twin_solve(bounded, calls, m, n, b, X, lo, hi, NULL, &o, NULL, NULL, NULL, NULL, info), 0);
       if (calls[3] < 4 && !g_fail_hits) { fprintf(stderr, "%d rounds\n", calls[3]); exit(1); } }
     o.mode = 2; o.maxfev = 3;          /* the round limit: maxfev + 2 rounds with every member still running */
-    { memset(calls, 0, sizeof calls); CALLS(fill_script("blm_update", (double) b, 8), qr_lstsq_lm_batched(lm_model, calls, m, n, b, X, D, &o, fn, nfev, njev, st, info), 0);
+    { memset(calls, 0, sizeof calls); CALLS(fill_script(upd, (double) b, 8), twin_solve(bounded, calls, m, n, b, X, lo, NULL, D, &o, fn, nfev, njev, st, info), 0);
       if (calls[3] != 5 && !g_fail_hits) { fprintf(stderr, "%d rounds at the limit\n", calls[3]); exit(1); } }
-    fill_script("blm_update", 0.0, 0);
+    fill_script(upd, 0.0, 0);
     for (int what = 1; what <= 3; ++what) {          /* the model fails: its code comes back, nothing leaks */
         memset(calls, 0, sizeof calls);
         calls[what] = 1; calls[0] = 1;
-        CALLX(qr_lstsq_lm_batched(lm_model, calls, m, n, b, X, D, &o, fn, nfev, njev, st, info), 77);
+        CALLX(twin_solve(bounded, calls, m, n, b, X, NULL, hi, D, &o, fn, nfev, njev, st, info), 77);
     }
     memset(calls, 0, sizeof calls);
     qrd_stub_set_info(4);
-    CALLX(qr_lstsq_lm_batched(lm_model, calls, m, n, b, X, NULL, NULL, fn, nfev, njev, st, info), QR_E_SINGULAR);
+    CALLX(twin_solve(bounded, calls, m, n, b, X, NULL, NULL, NULL, NULL, fn, nfev, njev, st, info), QR_E_SINGULAR);
     qrd_stub_set_info(0);
-    CALL(qr_lstsq_lm_batched(lm_model, calls, m, n, 0, X, NULL, NULL, fn, nfev, njev, st, info));
-    ARG(qr_lstsq_lm_batched(NULL, calls, m, n, b, X, NULL, NULL, fn, nfev, njev, st, info));
-    ARG(qr_lstsq_lm_batched(lm_model, calls, m, n, b, X, NULL, &o, fn, nfev, njev, st, info));          /* mode 2 without D */
-    ARG(qr_lstsq_lm_batched(lm_model, calls, n - 1, n, b, X, NULL, NULL, fn, nfev, njev, st, info));
+    if (bounded) {          /* two members that start refuses: QR_E_SINGULAR, and their X returns byte for byte as it came */
+        const double refused = 2.0;
+        double* X1 = hostd((size_t) n * b);
+        for (int i = 0; i < n * b; ++i) X[i] = X1[i] = 1.5 + i;
+        CALLS(qrd_stub_script("blmb_start", &refused, 1), twin_solve(1, calls, m, n, b, X, lo, hi, NULL, NULL, fn, nfev, njev, st, info), QR_E_SINGULAR);
+        if (memcmp(X, X1, sizeof(double) * 2 * (size_t) n) || info[0] != -2 || info[1] != -2 || info[2] != 0) {
+            fprintf(stderr, "a refused member's X or info: %d %d %d\n", info[0], info[1], info[2]); exit(1); }
+    }
+    CALL(twin_solve(bounded, calls, m, n, 0, X, NULL, NULL, NULL, NULL, fn, nfev, njev, st, info));
+    ARG(bounded ? qr_lstsq_lm_bounded_batched(NULL, calls, m, n, b, X, lo, hi, NULL, NULL, fn, nfev, njev, st, info)
+                : qr_lstsq_lm_batched(NULL, calls, m, n, b, X, NULL, NULL, fn, nfev, njev, st, info));
+    ARG(twin_solve(bounded, calls, m, n, b, X, lo, hi, NULL, &o, fn, nfev, njev, st, info));          /* mode 2 without D */
+    ARG(twin_solve(bounded, calls, n - 1, n, b, X, lo, hi, NULL, NULL, fn, nfev, njev, st, info));
 }
+static void blm_twin(void) { twin_on(0); }
+static void blmb_twin(void) { twin_on(1); }
 
 /* ================================================= threads (ThreadSanitizer) ================================================= */
-/* four host threads, different host-pointer twins: two share a shape (one cached slot, one private plan), two grow the slot's buffers */
+/* four host threads, different host-pointer twins: two share a shape (one cached slot, one private plan), two grow the slot's buffers; the
+ * first also runs the bounded Levenberg-Marquardt twin (a plan and a handle of its own per call) */
 static void* thread_body(void* arg)
 {
     const int id = (int) (size_t) arg, m = 40, n = 7, b = 5;
@@ -902,7 +972,8 @@ static void* thread_body(void* arg)
     for (int it = 0; it < 6; ++it) {
         const int nrhs = 1 + (it * 5 + id) % 17;
         switch (id) {
-        case 0: OK(qr_lstsq(A, m, n, B, nrhs, X, S)); break;
+        case 0: { int calls[4] = {0, 0, 0, 0}; OK(qr_lstsq(A, m, n, B, nrhs, X, S));
+                  OK(qr_lstsq_lm_bounded_batched(lm_model, calls, m, n, b, X, NULL, B, NULL, NULL, NULL, NULL, NULL, NULL, info)); break; }
         case 1: OK(qr_lstsq_svd(A, m, n, B, nrhs, -1.0, X, NULL, info, S)); break;          /* the same shape: the same slot, or a private plan */
         case 2: OK(qr_lstsq_pivoted(A, m, n, B, nrhs, -1.0, X, S, info, NULL)); OK(qr_lstsq_batched(A, m, n, B, 1, b, X, NULL, info)); break;
         default: { const int rc = qr_lstsq_minnorm(A, n, m, B, nrhs, X); if (rc && rc != QR_E_SINGULAR) OK(rc); OK(qr_svd(A, m, n, S, NULL, NULL)); break; }
@@ -936,6 +1007,7 @@ static const config g_cfg[] = {
     {"bconstrained_wave", bconstrained_wave}, {"bconstrained_wave_edge", bconstrained_wave_edge}, {"bconstrained_wg", bconstrained_wg},
     {"bconstrained_wg_cols", bconstrained_wg_cols}, {"bconstrained_limit", bconstrained_limit}, {"bconstrained_twins", bconstrained_twins},
     {"blm_wave", blm_wave}, {"blm_wave_edge", blm_wave_edge}, {"blm_wg", blm_wg}, {"blm_twin", blm_twin},
+    {"blmb_wave", blmb_wave}, {"blmb_wave_edge", blmb_wave_edge}, {"blmb_wg", blmb_wg}, {"blmb_twin", blmb_twin},
 };
 
 int main(int argc, char** argv)

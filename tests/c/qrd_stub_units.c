@@ -9,8 +9,9 @@
  * Scripted device words (the driver's hooks; without them every word stays as the stub's calloc left it, or at the value that ends a loop):
  *   qrd_stub_script(entry, values, n)   a queue per entry; "jsvd_fold": word[0] of the next calls; "jsvd_colnorms": the norms of the next
  *                                       call; "pivot_norms", "pivot_column": *pend after the call; "th_panel": *status (where it is still
- *                                       0); "blm_update": v members keep running (status 0), the others finish (status 1; v < 0: |v| keep
- *                                       running after a rejected step)
+ *                                       0); "blm_update", "blmb_update": v members keep running (status 0), the others finish (status 1;
+ *                                       v < 0: |v| keep running after a rejected step); "blmb_start": the first v members are refused
+ *                                       (info -2, nothing else of them written)
  *   qrd_stub_set_diag(d)                qrd_tp_panel / qrd_th_panel leave d on the diagonal of the triangle (0: untouched)
  *   qrd_stub_set_info(v)                every batched launch that owns info words writes v into them (0: untouched)
  *   qrd_stub_guard(p, bytes)            a write-tagged operand that meets [p, p + bytes) aborts (NULL: off) */
@@ -18,7 +19,7 @@
 
 static void misuse(const char* what, const char* why) { fprintf(stderr, "qrd_stub: %s: %s\n", what, why); abort(); }
 
-#define NSCRIPT 8
+#define NSCRIPT 12
 static struct { const char* entry; double v[128]; int n, at; } g_script[NSCRIPT];
 static pthread_mutex_t g_smu = PTHREAD_MUTEX_INITIALIZER;
 static double g_diag;
@@ -622,7 +623,7 @@ int qrd_bt_fused(void* s, double* A, int m, int lda, size_t sA, double* tau, siz
     return 0;
 }
 
-/* ---- qr_batched_lm.hip ---- */
+/* ---- qr_batched_lm.hip: sections 8m (qrd_blm_*) and 8n (qrd_blmb_*) ---- */
 static int blm_bad_state(const qrd_blm_state* s)
 {
     return !s->x || !s->xtrial || !s->D || !s->delta || !s->par || !s->fnorm || !s->xnorm || !s->pnorm || !s->gnorm || !s->prered || !s->dirder ||
@@ -659,20 +660,83 @@ int qrd_blm_step(void* s, const qrd_blm_step_args* a)
     bd_in(d, 1); blm_state_chk(&a->s, d->n, d->batch);
     return 0;
 }
-int qrd_blm_update(void* s, const double* Ft, int m, int ldf, size_t sF, int n, int batch, const qrd_blm_state* st, const qrd_blm_opts* o)
+/* the words an update leaves, from the script of `entry` ("blm_update", "blmb_update") */
+static void blm_update_words(const char* entry, const qrd_blm_state* st, int batch)
 {
-    if (batch <= 0) return 0;
-    if (!st || !o || blm_bad_state(st) || !Ft || n < 1 || n + 1 > QRD_B_MAX_N || m < 1 || ldf < m) return -7;
-    op_begin(s, "blm_update");
-    chks("blm_update Ft", Ft, sF, ldf, m, 1, batch, RD, 0); blm_state_chk(st, n, batch);
     double v = 0.0;
-    const int scripted = script_take("blm_update", &v);
+    const int scripted = script_take(entry, &v);
     const int running = scripted ? (int) (v < 0.0 ? -v : v) : 0;          /* unscripted: every member finishes, the host loop ends */
     for (int q = 0; q < batch; ++q) {
         st->status[q] = q < running ? 0 : 1;
         st->accepted[q] = !(scripted && v < 0.0);
         if (g_info) st->info[q] = g_info;
     }
+}
+int qrd_blm_update(void* s, const double* Ft, int m, int ldf, size_t sF, int n, int batch, const qrd_blm_state* st, const qrd_blm_opts* o)
+{
+    if (batch <= 0) return 0;
+    if (!st || !o || blm_bad_state(st) || !Ft || n < 1 || n + 1 > QRD_B_MAX_N || m < 1 || ldf < m) return -7;
+    op_begin(s, "blm_update");
+    chks("blm_update Ft", Ft, sF, ldf, m, 1, batch, RD, 0); blm_state_chk(st, n, batch);
+    blm_update_words("blm_update", st, batch);
+    return 0;
+}
+/* section 8n: the same state, then lo, hi, alpha, peg and clipped */
+static int blmb_bad_state(const qrd_blmb_state* s) { return blm_bad_state(&s->b) || !s->lo || !s->hi || !s->alpha || !s->peg || !s->clipped; }
+static void blmb_state_chk(const qrd_blmb_state* s, int n, int b)
+{
+    blm_state_chk(&s->b, n, b);
+    chk("blmb state lo", s->lo, (long) n * b, (long) n * b, 1, RW); chk("blmb state hi", s->hi, (long) n * b, (long) n * b, 1, RW);
+    chk("blmb state alpha", s->alpha, b, b, 1, RW);
+    chkb("blmb state peg", s->peg, sizeof(int) * (size_t) n * (size_t) b, RW); chkb("blmb state clipped", s->clipped, sizeof(int) * (size_t) b, RW);
+}
+int qrd_blmb_start(void* s, const double* X0, int ldx, size_t sX, const double* D0, size_t sD, const double* Lo, size_t sLo, const double* Hi,
+                   size_t sHi, int n, int batch, const qrd_blmb_state* st, int mode)
+{
+    if (batch <= 0) return 0;
+    if (!st || blmb_bad_state(st) || !X0 || n < 1 || n + 1 > QRD_B_MAX_N || ldx < n || (mode == 2 && !D0)) return -7;
+    op_begin(s, "blmb_start");
+    chkv("blmb_start X0", X0, sX, n, batch, RD, 0);
+    if (mode == 2) chkv("blmb_start D0", D0, sD, n, batch, RD, 1);
+    if (Lo) chkv("blmb_start Lo", Lo, sLo, n, batch, RD, 1);
+    if (Hi) chkv("blmb_start Hi", Hi, sHi, n, batch, RD, 1);
+    blmb_state_chk(st, n, batch);
+    double v = 0.0;
+    const int refused = script_take("blmb_start", &v) ? (int) v : 0;      /* the first v members: bounds that are no box, nothing else written */
+    for (int q = 0; q < batch; ++q) {
+        if (q < refused) { st->b.info[q] = -2; continue; }
+        st->b.status[q] = 0; st->b.info[q] = 0;
+    }
+    return 0;
+}
+int qrd_blmb_peg(void* s, double* J, int m, int ldj, size_t sJ, const double* F, size_t sF, int n, int batch, const qrd_blmb_state* st)
+{
+    if (batch <= 0) return 0;
+    if (!st || blmb_bad_state(st) || !J || !F || n < 1 || n + 1 > QRD_B_MAX_N || m < 1 || ldj < m || sJ < (size_t) ldj * (size_t) n || sF < (size_t) m)
+        return -7;
+    op_begin(s, "blmb_peg");
+    chks("blmb_peg J", J, sJ, ldj, m, n, batch, RW, 0); chkv("blmb_peg F", F, sF, m, batch, RD, 0);
+    blmb_state_chk(st, n, batch);
+    return 0;
+}
+int qrd_blmb_step(void* s, const qrd_blmb_step_args* a)
+{
+    if (!a || a->d.batch <= 0) return 0;
+    const qrd_bd_args* d = &a->d;
+    if (d->n < 1 || d->n + 1 > QRD_B_MAX_N || d->nrhs != 1 || d->nlam != 1 || !d->R || !d->Z || d->ldr < d->n || d->zrows < d->n ||
+        d->ldz < d->zrows || d->flip || d->D || blmb_bad_state(&a->s) || !(a->o.par_rtol > 0.0 && a->o.par_rtol < 1.0) || a->o.par_maxit < 1)
+        return -7;
+    op_begin(s, "blmb_step");
+    bd_in(d, 1); blmb_state_chk(&a->s, d->n, d->batch);
+    return 0;
+}
+int qrd_blmb_update(void* s, const double* Ft, int m, int ldf, size_t sF, int n, int batch, const qrd_blmb_state* st, const qrd_blm_opts* o)
+{
+    if (batch <= 0) return 0;
+    if (!st || !o || blmb_bad_state(st) || !Ft || n < 1 || n + 1 > QRD_B_MAX_N || m < 1 || ldf < m) return -7;
+    op_begin(s, "blmb_update");
+    chks("blmb_update Ft", Ft, sF, ldf, m, 1, batch, RD, 0); blmb_state_chk(st, n, batch);
+    blm_update_words("blmb_update", &st->b, batch);
     return 0;
 }
 

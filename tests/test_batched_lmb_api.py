@@ -36,32 +36,47 @@ def test_header_declares_and_library_exports_the_calls(qr):
 
 
 def test_the_unit_is_built_beside_the_stubbed_units_and_shares_the_rules():
+    """Sections 8m and 8n are one host unit and one kernel file: the unit runs over the stub device layer with the others, the step is one
+    kernel pair instantiated twice, and the rules of section 8m are written once."""
+    import glob
+    import re
     mk = open(os.path.join(ROOT, "cuda-qr_amd", "Makefile")).read()
-    assert "csrc/qr_batched_lmb.c" not in mk.split("\nCSRC =")[1].splitlines()[0]              # CSRC is what the stub builds compile
-    assert "csrc/qr_batched_lmb.c" in mk.split("\nCSRC_DEVICE_ONLY =")[1].splitlines()[0]
-    assert "$(CSRC_DEVICE_ONLY:csrc/%.c=build/%_c.o)" in mk.split("\nOBJS =")[1].splitlines()[0]
+    csrc_line = mk.split("\nCSRC =")[1].splitlines()[0].split()
+    assert "csrc/qr_batched_lm.c" in csrc_line                                                 # CSRC is what the stub builds compile:
+    assert mk.split("\nUNITS_LIB =")[1].splitlines()[0].split() == ["csrc/qr_host.c", "$(CSRC)"]      # UNITS_LIB
+    assert "build/qr_batched_lm_c.o" in mk.split("\nOBJS =")[1].splitlines()[0].split()
     lab = mk.split("\nLAB_OBJS =")[1]
-    assert "$(CSRC_DEVICE_ONLY:csrc/%.c=build/lab/%_c.o)" in lab[:lab.index("$(LAB):")]
-    assert "CSRC_DEVICE_ONLY" not in mk.split("\nUNITS_LIB =")[1].splitlines()[0]
-    assert "qr_batched_lmb" in mk.split("HIPSRC =")[1].splitlines()[0].split()
+    assert "build/lab/qr_batched_lm_c.o" in lab[:lab.index("$(LAB):")].split()
+    assert "CSRC_DEVICE_ONLY" not in mk and "qr_batched_lmb" not in mk
+    assert "qr_batched_lm" in mk.split("HIPSRC =")[1].splitlines()[0].split()
     assert "csrc/qr_batched_lm_dev.h" in mk.split("\nHDRS =")[1].splitlines()[0]
-    for f in ("qr_host.c", "qr_batched_lm.c"):
-        assert "qrd_blmb_" not in open(os.path.join(CSRC, f)).read(), f
+    for gone in ("qr_batched_lmb.c", "qr_batched_lmb.hip"):
+        assert not os.path.exists(os.path.join(CSRC, gone)), gone
+    assert "qrd_blmb_" not in open(os.path.join(CSRC, "qr_host.c")).read()
     dev = open(os.path.join(CSRC, "qr_device.h")).read()
     for w in ("qrd_blmb_start", "qrd_blmb_peg", "qrd_blmb_step", "qrd_blmb_update", "qrd_blmb_state", "qrd_blmb_step_args"):
         assert w in dev
-    unit = open(os.path.join(CSRC, "qr_batched_lmb.c")).read()
-    assert "qr_stage_open" in unit and "qrd_blmb_peg" in unit and unit.index("qrd_blmb_peg(") < unit.index("qrd_b_geqp3(")
+    unit = open(os.path.join(CSRC, "qr_batched_lm.c")).read()
+    assert "qr_stage_open" in unit and unit.count("qr_stage_open(") == 1                       # one driver loop for both twins
+    for call in ("qrd_blmb_peg(", "qrd_b_geqp3(", "qrd_b_ormqr(", "qrd_blm_step(", "qrd_blmb_step(", "qrd_blm_start(", "qrd_blmb_start(",
+                 "qrd_blm_update(", "qrd_blmb_update("):
+        assert unit.count(call) == 1, call                                                     # every launch is made in one place
+    assert unit.index("qrd_blmb_peg(") < unit.index("qrd_b_geqp3(") < unit.index("qrd_b_ormqr(")      # the bounded step path: the peg first
+    step = unit[unit.index("static int lm_step("):unit.index("static int lm_update(")]
+    assert "qrd_blmb_peg(" in step and "qrd_b_geqp3(" in step and "lm_step_launch(" in step
     hdr = open(os.path.join(CSRC, "qr_batched_lm_dev.h")).read()
     lm = open(os.path.join(CSRC, "qr_batched_lm.hip")).read()
-    lmb = open(os.path.join(CSRC, "qr_batched_lmb.hip")).read()
     for fn in ("blm_scalars", "blm_finish", "blm_fail", "blm_update_member", "blm_start_member"):
         assert "void " + fn + "(" in hdr, fn
-        for f in (lm, lmb):                                                                   # called in both files, defined in neither
-            assert fn + "(" in f and "void " + fn + "(" not in f, fn
-    for f in (lm, lmb):
-        assert '#include "qr_batched_lm_dev.h"' in f and "bt_wave_core" in f and "bt_wg_core" in f
-        assert "actred" not in f and "temp2" not in f                                          # the update and rule h live in the header alone
+        assert fn + "(" in lm and "void " + fn + "(" not in lm, fn                            # called in the kernels' file, defined in the header
+    assert '#include "qr_batched_lm_dev.h"' in lm
+    assert "actred" not in lm and "temp2" not in lm                                            # the update and rule h live in the header alone
+    every = "".join(open(f).read() for f in sorted(glob.glob(os.path.join(CSRC, "*"))))
+    for kernel in ("blm_step_wave_kernel", "blm_step_wg_kernel"):                              # one kernel pair, two instantiations
+        assert len(re.findall(r"__global__\s+void\s+(?:__launch_bounds__\(\d+\)\s+)?" + kernel + r"\b", every)) == 1, kernel
+    assert "blmb_step_wave_kernel" not in every and "blmb_step_wg_kernel" not in every
+    for core in ("bt_wave_core", "bt_wg_core"):                                                # each search is called exactly once
+        assert len(re.findall(core + r"\s*(?:<\w+>)?\(", lm)) == 1, core
 
 
 class _FakePlan(C.Structure):

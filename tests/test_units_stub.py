@@ -1,4 +1,5 @@
-"""The seventeen per-interface host units (qr_solve.c ... qr_batched_lm.c) over the stub device layer, checked without a GPU.
+"""The seventeen per-interface host units (qr_solve.c ... qr_batched_lm.c, the last one both Levenberg-Marquardt sections, 8m and 8n) over
+the stub device layer, checked without a GPU.
 
 The stub (tests/c/qrd_stub.c, tests/c/qrd_stub_units.c) has an entry for every launch these units make: it refuses the shapes the real
 launcher refuses, bounds-checks every operand block at the extent qr_device.h documents and stamps it for the stream-order model.  The
