@@ -608,7 +608,7 @@ __global__ void __launch_bounds__(256) bp_rank_kernel(const double* __restrict__
     rank[q] = r;
 }
 
-// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernels that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int b_allow_lds(void)
 {
     static std::atomic<int> done[64];
@@ -617,7 +617,7 @@ static int b_allow_lds(void)
                                reinterpret_cast<const void*>(b_ormqr_kernel<8>), reinterpret_cast<const void*>(b_wave_kernel<32>),
                                reinterpret_cast<const void*>(bp_wg_kernel),      reinterpret_cast<const void*>(bp_wave_kernel<32>),
                                reinterpret_cast<const void*>(bp_solve_kernel)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 template <int W>

@@ -448,12 +448,12 @@ __global__ void __launch_bounds__(256) bv_wg_kernel(const qrd_bv_args g)
     }
 }
 
-// the kernel that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernel that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int bv_allow_lds(void)
 {
     static std::atomic<int> done[64];
     const void* const fns[] = {reinterpret_cast<const void*>(bv_wg_kernel)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 template <int W>

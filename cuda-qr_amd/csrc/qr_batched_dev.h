@@ -1,7 +1,7 @@
 // qr_batched_dev.h -- the device code that the batched kernel files (qr_batched.hip, qr_batched_update.hip, qr_batched_minnorm.hip,
 // qr_batched_svd.hip, qr_batched_damped.hip, qr_batched_trust.hip, qr_batched_lse.hip, qr_batched_bvls.hip, qr_batched_irls.hip, qr_batched_stats.hip, qr_batched_lsei.hip) share: the wave helpers, the dlarfg scalars, the Householder column step of the wave route and of the workgroup
 // route, one reflector on a column in registers, the triangular solves over an LDS image, the info word, the elimination of a damping block (shared by the damped and the
-// trust-region kernels; the search itself, which qr_batched_lm.hip runs as well, is qr_batched_trust_dev.h), and the LDS opt-in.  No
+// trust-region kernels; the search itself, which qr_batched_lm.hip runs as well, is qr_batched_trust_dev.h), and the LDS cap.  No
 // kernels, no entry points.  Two kernels that call the same step here run the same operations in the same order: that is what makes
 // the factors and tau of qrd_b_geqrf, qrd_b_geqp3 (on the permuted columns) and qrd_bm_fused equal bit for bit on the same route.
 //
@@ -11,12 +11,10 @@
 
 #include <float.h>
 
-#include <atomic>
-
 #include "qr_common.h"
 #include "qr_device.h"
 
-#define QB_LDS_CAP (160 * 1024)           // what one workgroup may hold, once allowed (qb_allow_lds)
+#define QB_LDS_CAP (160 * 1024)           // what one workgroup may hold, once allowed (qr_allow_lds, qr_common.h)
 #define QB_WG_SMALL 72                    // doubles beside the image of a workgroup route: red[4], words, 64 per-column values; qrd_b_fits budgets them
 
 #define QB_WAVE_SYNC()                                           \
@@ -446,23 +444,6 @@ __device__ __forceinline__ void bd_wg_elim(const double* Ms, double* Ws, double*
         __syncthreads();                  // (alpha and column j of the block are read no more)
         if (t == 0 && ssq != 0.0) Ws[j * ld + j] = beta;    // (read next by thread 0 below, by the others after a barrier)
     }
-}
-
-// More than 64 KiB of LDS per workgroup has to be allowed per kernel and device, once: `done` is the calling file's own record of the
-// devices on which every kernel of its table `fns` has been allowed.  Returns 0 or the HIP error.
-template <size_t N>
-static inline int qb_allow_lds(const void* const (&fns)[N], std::atomic<int> (&done)[64])
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int) e;
-    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
-    for (const void* f : fns) {
-        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, QB_LDS_CAP);
-        if (e != hipSuccess) return (int) e;
-    }
-    if (dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
-    return 0;
 }
 
 #endif

@@ -339,13 +339,13 @@ __global__ void __launch_bounds__(256) blmb_start_kernel(const double* __restric
 
 static int blmb_bad_state(const qrd_blmb_state* s) { return blm_bad_state(&s->b) || !s->lo || !s->hi || !s->alpha || !s->peg || !s->clipped; }
 
-// the kernels of one instantiation that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernels of one instantiation that may ask for more than 64 KiB of LDS (qr_allow_lds)
 template <class A>
 static int blm_allow_lds(void)
 {
     static std::atomic<int> done[64];
     const void* const fns[] = {reinterpret_cast<const void*>(blm_step_wg_kernel<A>), reinterpret_cast<const void*>(blm_step_wave_kernel<32, A>)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 // the step of every running member from factors that exist: one launch.  -7: shape not taken.  bad_state: the refusal of A's state struct

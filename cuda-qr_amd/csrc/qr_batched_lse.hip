@@ -314,12 +314,12 @@ __global__ void __launch_bounds__(256) bl_wg_kernel(const qrd_bl_args g)
     }
 }
 
-// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernels that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int bl_allow_lds(void)
 {
     static std::atomic<int> done[64];
     const void* const fns[] = {reinterpret_cast<const void*>(bl_wg_kernel), reinterpret_cast<const void*>(bl_wave_kernel<32>)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 template <int W>

@@ -721,12 +721,12 @@ __global__ void __launch_bounds__(256) le_wg_kernel(const qrd_le_args g)
     }
 }
 
-// the kernel that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernel that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int le_allow_lds(void)
 {
     static std::atomic<int> done[64];
     const void* const fns[] = {reinterpret_cast<const void*>(le_wg_kernel)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 template <int W>

@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(256) bm_transpose_kernel(const double* __restr
     }
 }
 
-// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernels that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int bm_allow_lds(void)
 {
     static std::atomic<int> done[64];
@@ -259,7 +259,7 @@ static int bm_allow_lds(void)
                                reinterpret_cast<const void*>(bm_apply_kernel<8>),
                                reinterpret_cast<const void*>(bm_wave_kernel<32, false>),
                                reinterpret_cast<const void*>(bm_wave_kernel<32, true>)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 template <int W>

@@ -573,7 +573,7 @@ __global__ void __launch_bounds__(256) bs_fit_wg_kernel(const qrd_bs_fit_args g)
     if (t == 0) g.info[q] = 0;
 }
 
-// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernels that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int st_allow_lds(void)
 {
     static std::atomic<int> done[64];
@@ -581,7 +581,7 @@ static int st_allow_lds(void)
                                reinterpret_cast<const void*>(bs_fit_wg_kernel<24>), reinterpret_cast<const void*>(bs_fit_wg_kernel<32>),
                                reinterpret_cast<const void*>(bs_fit_wg_kernel<40>), reinterpret_cast<const void*>(bs_fit_wg_kernel<48>),
                                reinterpret_cast<const void*>(bs_fit_wg_kernel<56>), reinterpret_cast<const void*>(bs_fit_wg_kernel<64>)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 template <int W>

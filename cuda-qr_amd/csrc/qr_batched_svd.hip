@@ -27,7 +27,7 @@
 // group): results are bitwise repeatable, independent of `batch` and of a matrix's index, and sigma does not depend on whether W is
 // accumulated.  No atomics, nothing crosses a workgroup, nothing spins.
 //
-// From qr_batched_dev.h: the wave helpers, the dlarfg scalars (bs_house) and the LDS opt-in.
+// From qr_batched_dev.h: the wave helpers, the dlarfg scalars (bs_house) and the LDS cap; the opt-in is qr_common.h's.
 //
 // Out of scope: a single launch fused with the factorisation and with the product by Q; wide matrices; n > 64.
 #include <float.h>
@@ -252,12 +252,12 @@ __global__ void __launch_bounds__(256) bs_jsvd_kernel(const double* __restrict__
 #undef BS_SYNC
 }
 
-// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernels that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int bs_allow_lds(void)
 {
     static std::atomic<int> done[64];
     const void* const fns[] = {reinterpret_cast<const void*>(bs_jsvd_kernel<false>), reinterpret_cast<const void*>(bs_jsvd_kernel<true>)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 extern "C" {

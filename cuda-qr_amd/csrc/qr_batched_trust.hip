@@ -155,13 +155,13 @@ __global__ void __launch_bounds__(256) bt_wg_kernel(const qrd_bt_args a)
     }
 }
 
-// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernels that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int bt_allow_lds(void)
 {
     static std::atomic<int> done[64];
     const void* const fns[] = {reinterpret_cast<const void*>(bt_wg_kernel), reinterpret_cast<const void*>(bt_wave_kernel<32>),
                                reinterpret_cast<const void*>(bt_fused_wave_kernel<32>)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 static int bt_bad_args(const qrd_bt_args* a)

@@ -6,7 +6,7 @@
 //                      registers, lane j < n holds row j of [R | Z] in W more; sums are wave butterflies; no LDS, no barrier
 //   bu_wg_kernel       everything else within qr_tpqrt_batched_max_rows: one workgroup per member, [B | C2] resident in LDS at a leading
 //                      dimension of 2 mod 32 and [R | Z] beside it at an odd one; thread t owns block row t (th_panel_kernel,
-//                      qr_downdate.hip, without T); the trailing update is rank-1, one wave per column
+//                      qr_update.hip, without T); the trailing update is rank-1, one wave per column
 //   bu_apply_kernel    the stored reflectors applied to later right-hand sides [C1 ; C2], V and tau resident in LDS, one wave per column
 //   bu_solve_prep_kernel   X <- Z and resid <- sqrt(rss) per member, ahead of qrd_b_trsm
 //
@@ -27,7 +27,7 @@
 // Every sum runs in a fixed order that (n, nrhs, p_add, p_del) alone fix (wave butterflies, waves added in wave order, serial loops):
 // repeated launches are bitwise equal and a member's result does not depend on the batch count or its index.  No atomics.
 //
-// From qr_batched_dev.h: the wave helpers, the leading dimension and the LDS opt-in.  The column step and its scalars are this file's
+// From qr_batched_dev.h: the wave helpers, the leading dimension and the LDS cap (the opt-in is qr_common.h's).  The column step and its scalars are this file's
 // own: the signed sums and bu_hypot are another formula than dlarfg's, on purpose.
 #include "qr_batched_dev.h"
 
@@ -350,13 +350,13 @@ __global__ void __launch_bounds__(256) bu_solve_prep_kernel(const double* __rest
         for (int c = threadIdx.x; c < nrhs; c += 256) resid[q * strideresid + c] = sqrt(rss[q * (size_t) nrhs + c]);
 }
 
-// the kernels that may ask for more than 64 KiB of LDS (qb_allow_lds)
+// the kernels that may ask for more than 64 KiB of LDS (qr_allow_lds)
 static int bu_allow_lds(void)
 {
     static std::atomic<int> done[64];
     const void* const fns[] = {reinterpret_cast<const void*>(bu_wg_kernel), reinterpret_cast<const void*>(bu_apply_kernel<1>),
                                reinterpret_cast<const void*>(bu_apply_kernel<2>), reinterpret_cast<const void*>(bu_apply_kernel<4>)};
-    return qb_allow_lds(fns, done);
+    return qr_allow_lds(fns, QB_LDS_CAP, done);
 }
 
 extern "C" {

@@ -1,7 +1,9 @@
-// qr_common.h -- device helpers shared by the HIP translation units
+// qr_common.h -- device helpers shared by the HIP translation units, and the host's LDS opt-in
 #ifndef QR_COMMON_H
 #define QR_COMMON_H
 #include <hip/hip_runtime.h>
+
+#include <atomic>
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
@@ -103,6 +105,25 @@ __device__ __forceinline__ void tile_of_block(int bid, int gx, int gy, int gm, i
         tx = id % gx;
         ty = id / gx;
     }
+}
+
+// ---- LDS opt-in (host) ----------------------------------------------------------------------------------
+// More than 64 KiB of LDS per workgroup has to be allowed per kernel and device, once: `done` is the caller's own record of the
+// devices on which every kernel of its table `fns` has been allowed `bytes`.  Atomic, because plans may be driven from several host
+// threads (two that meet here both set the attribute, which is harmless).  Returns 0 or the HIP error.
+template <size_t N>
+static inline int qr_allow_lds(const void* const (&fns)[N], int bytes, std::atomic<int> (&done)[64])
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int) e;
+    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
+    for (const void* f : fns) {
+        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return (int) e;
+    }
+    if (dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
+    return 0;
 }
 
 #endif

@@ -242,7 +242,7 @@ int qrd_tp_apply(void* stream, int trans_t, const double* Vk, int ldv, int p, in
 int qrd_tp_colssq_add(void* stream, const double* X, int ldx, int rows, int cols, double* acc);
 int qrd_tp_sqrt(void* stream, const double* in, double* out, int n);
 
-/* signed-row update (qr_downdate.hip, called from qr_downdate.c only): the rows
+/* signed-row update (the signed instances in qr_update.hip, called from qr_downdate.c only): the rows
  * [0, p_add) of a block count +1, the rows [p_add, p) count -1 (S = diag of those signs).  status: one device int, 0 while all is well;
  * every launch reads it first and returns at once when it is not 0.
  * qrd_th_panel: qrd_tp_panel with every inner product over the p rows weighted by S; a column whose d = R(j,j)^2 + b^T S b is <= 0 or

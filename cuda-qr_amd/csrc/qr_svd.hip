@@ -352,17 +352,12 @@ __global__ void jsvd_rt_kernel(const double* __restrict__ A, int lda, int n, dou
     if (i < n) W[(size_t) j * ldw + i] = i >= j ? A[(size_t) i * lda + j] : 0.0;
 }
 
-// more than 64 KiB of LDS per workgroup has to be allowed per kernel and device, once
+// the kernel that asks for more than 64 KiB of LDS (qr_allow_lds)
 static int js_allow_lds(void)
 {
-    static int done[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int) e;
-    if (dev >= 0 && dev < 64 && done[dev]) return 0;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(jsvd_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) JS_PAIR_LDS);
-    if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = 1;
-    return (int) e;
+    static std::atomic<int> done[64];
+    const void* const fns[] = {reinterpret_cast<const void*>(jsvd_pair_kernel)};
+    return qr_allow_lds(fns, (int) JS_PAIR_LDS, done);
 }
 
 extern "C" {

@@ -36,15 +36,23 @@ def test_notpd_status_is_defined_and_named(qr):
     assert "positive-definite" in s and s != qr.strerror(-9999)
 
 
-def test_host_code_stays_out_of_the_stubbed_translation_unit():
-    """qr_host.c is compiled against the stub device layer by the sanitizer builds: the new launch wrappers must not be called from it"""
+def test_host_code_stays_out_of_the_stubbed_translation_unit(qr):
+    """qr_host.c is compiled against the stub device layer by the sanitizer builds: the new launch wrappers must not be called from it.
+    The kernels of this interface are the signed instances in qr_update.hip: no file of their own, and the library has their launchers."""
     src = open(os.path.join(ROOT, "cuda-qr_amd", "csrc", "qr_host.c")).read()
     assert "qrd_th_" not in src
     mk = open(os.path.join(ROOT, "cuda-qr_amd", "Makefile")).read()
     assert "build/qr_downdate_c.o" in mk.split("\nOBJS =")[1].splitlines()[0]
     lab = mk.split("\nLAB_OBJS =")[1]
     assert "build/lab/qr_downdate_c.o" in lab[:lab.index("$(LAB):")]
-    assert "csrc/qr_downdate.c" in mk and "qr_downdate" in mk.split("HIPSRC =")[1].splitlines()[0].split()
+    assert "csrc/qr_downdate.c" in mk
+    hipsrc = mk.split("HIPSRC =")[1].splitlines()[0].split()
+    assert "qr_update" in hipsrc
+    assert "qr_downdate" not in hipsrc
+    assert not os.path.exists(os.path.join(ROOT, "cuda-qr_amd", "csrc", "qr_downdate.hip"))
+    out = subprocess.run(["nm", "-D", qr.LIB_PATH], capture_output=True, text=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    assert {"qrd_th_panel", "qrd_th_apply", "qrd_th_colssq"} <= exported
 
 
 class _FakePlan(C.Structure):
