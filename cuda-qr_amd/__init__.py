@@ -339,6 +339,24 @@ _sig("qrd_transpose", C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int
 _sig("qrd_copy_block", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int)
 _sig("qrd_init", C.c_int)
 _sig("qrd_device_sync", C.c_int)
+if hasattr(lib, "qrd_tp_panel"):        # (absent from libraries of earlier commits loaded for A/B runs through CUDA_QR_AMD_LIB)
+    _sig("qrd_tp_panel", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int)
+    _sig("qrd_tp_apply", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
+    _sig("qrd_tp_colssq_add", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+    _sig("qrd_tp_sqrt", C.c_int, _vp, _vp, _vp, C.c_int)
+if hasattr(lib, "qrd_th_panel"):
+    _sig("qrd_th_panel", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp)
+    _sig("qrd_th_apply", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp)
+    _sig("qrd_th_colssq", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp)
+if hasattr(lib, "qrd_jsvd_round"):
+    _sig("qrd_jsvd_round", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp)
+    _sig("qrd_jsvd_fold", C.c_int, _vp, _vp, C.c_int, _vp)
+    _sig("qrd_jsvd_colnorms", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+    _sig("qrd_jsvd_gather", C.c_int, _vp, _vp, _vp, _vp, C.c_int)
+    _sig("qrd_jsvd_permute", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+    _sig("qrd_jsvd_normalise", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+    _sig("qrd_jsvd_pinv_scale", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_double)
+    _sig("qrd_jsvd_rt", C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int)
 
 
 def strerror(rc):

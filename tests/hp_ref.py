@@ -6,6 +6,9 @@ that the GPU tests measure the kernels' errors against.  The Householder convent
 ||x||, tau = (beta - alpha) / beta, v = x / (alpha - beta) with a unit head, an exactly zero tail gives tau = 0) without dlarfg's
 rescaling of tiny vectors.  Sums of squares are plain `(x * x).sum()`: for a power of two s every function here is exactly
 homogeneous while nothing leaves the normal range, which tests/test_hp_ref.py asserts bitwise.
+
+The last block restates single kernels rather than entry points, for the launch-layer tests (test_gpu_update_kernels.py,
+test_gpu_svd_kernels.py): tp_panel and tp_apply in the convention of csrc/qr_update.hip, jacobi_pair after jsvd_pair_kernel.
 """
 import numpy as np
 
@@ -266,3 +269,159 @@ def normal_equations_residual(A, X, B):
     g = matmul(A.T, matmul(A, X) - B)
     nA = norm(A)
     return max(float(norm(g[:, j]) / (nA * nA * norm(X[:, j]) + nA * norm(B[:, j]))) for j in range(X.shape[1]))
+
+
+# ---- the launch layer of the row updates and of the Jacobi SVD (csrc/qr_update.hip, csrc/qr_svd.hip) ----------------------------------
+def _signs(p, p_add, dtype):
+    """the diagonal of S: +1 for the block's first p_add rows, -1 for the others"""
+    s = arr(np.ones(p), dtype)
+    s[p_add:] = -s[p_add:]
+    return s
+
+
+def tp_panel(R, B, p_add=None, dtype=LD):
+    """(R', V, T) of the panel [R (w x w upper triangle) ; B (p x w)] under the signs S = diag(+1 (p_add times), -1), the convention at
+    the top of csrc/qr_update.hip: reflector j is I - tau_j u_j u_j^T Phi with u_j = [e_j ; V(:, j)], Phi = diag(I, S);
+    d = alpha^2 + b^T S b, beta = -sign(alpha) sqrt(d), tau = (beta - alpha) / beta, v = b / (alpha - beta); every product over the
+    block's rows is weighted by S; T by dlarft, forward columnwise, with those weighted dots.  p_add = p (the default) is the unsigned
+    instance.  An exactly zero column of B gives tau = 0 and changes nothing; d <= 0 raises ArithmeticError with the column in args[1]."""
+    Rn, V = arr(triu(R), dtype), arr(B, dtype)
+    p, w = V.shape
+    p_add = p if p_add is None else p_add
+    s = _signs(p, p_add, dtype)
+    T = arr(np.zeros((w, w)), dtype)
+    for j in range(w):
+        b = V[:, j]
+        if not np.any(b != 0):
+            continue
+        alpha = Rn[j, j]
+        d = alpha * alpha + (s * b * b).sum()
+        if not d > 0:
+            raise ArithmeticError("no positive-definite triangle is left", j)
+        beta = -_root(d, dtype) if alpha >= 0 else _root(d, dtype)
+        tau = (beta - alpha) / beta
+        V[:, j] = b / (alpha - beta)
+        Rn[j, j] = beta
+        sv = s * V[:, j]
+        for c in range(j + 1, w):
+            tw = tau * (Rn[j, c] + (sv * V[:, c]).sum())
+            Rn[j, c] -= tw
+            V[:, c] -= tw * V[:, j]
+        dots = [(sv * V[:, l]).sum() for l in range(j)]
+        for i in range(j):
+            T[i, j] = -tau * sum(T[i, l] * dots[l] for l in range(i, j))
+        T[j, j] = tau
+    return Rn, V, T
+
+
+def tp_apply(V, T, C1, C2, p_add=None, trans=1, dtype=LD):
+    """(C1 - W, C2 - V W) with W = op(T) (C1 + V^T S C2): V p x w, T w x w (only its upper triangle is read), C1 w x ncols, C2 p x ncols.
+    op(T) = T^T for trans != 0 and whenever the call is signed (p_add < p), else T."""
+    V, C1, C2 = arr(V, dtype), arr(C1, dtype), arr(C2, dtype)
+    p, w = V.shape
+    p_add = p if p_add is None else p_add
+    s = _signs(p, p_add, dtype)
+    Tu = arr(np.zeros((w, w)), dtype)
+    for j in range(w):
+        Tu[:j + 1, j] = arr(np.asarray(T)[:j + 1, j], dtype)
+    op = Tu.T if (trans or p_add < p) else Tu
+    W0 = C1.copy()
+    for i in range(p):
+        W0 += (s[i] * V[i])[:, None] * C2[i][None, :]
+    W = W0 * 0
+    for k in range(w):
+        W += op[:, k][:, None] * W0[k][None, :]
+    C2n = C2.copy()
+    for k in range(w):
+        C2n -= V[:, k][:, None] * W[k][None, :]
+    return C1 - W, C2n
+
+
+JS_SLOTS = 64                 # a block pair of csrc/qr_svd.hip: two blocks of 32 columns
+JS_INNER_MAX = 16
+
+
+def js_live(a, b):
+    """the columns of squared norms a, b take part in the measure and are rotated: neither is negligible beside the other"""
+    e2 = EPS * EPS
+    return a > 0 and b > 0 and a > e2 * b and b > e2 * a
+
+
+def js_inner_pair(st, k):
+    """the k-th of the 32 disjoint index pairs (i < j) of step st (0 .. 62) of the round-robin over 64 indices: 63 stays, the others turn"""
+    m = JS_SLOTS - 1
+    a, b = (st, m) if k == 0 else ((st + k) % m, (st - k + m) % m)
+    return min(a, b), max(a, b)
+
+
+def gram_measure(S, dtype=LD):
+    """max over the live pairs i < j of |s_ij| / (sqrt(s_ii) sqrt(s_jj))"""
+    k = S.shape[0]
+    rt = _root(arr([S[i, i] if S[i, i] > 0 else 0 for i in range(k)], dtype), dtype)
+    v = S[0, 0] * 0
+    for j in range(k):
+        for i in range(j):
+            if js_live(S[i, i], S[j, j]):
+                v = max(v, abs(S[i, j]) / (rt[i] * rt[j]))
+    return v
+
+
+def gram(G, dtype=LD):
+    G = arr(G, dtype)
+    S = arr(np.zeros((G.shape[1], G.shape[1])), dtype)
+    for i in range(G.shape[0]):
+        S += G[i][:, None] * G[i][None, :]
+    return S
+
+
+def pair_measure(G, dtype=LD):
+    """the measure of the columns of G (the Gram matrix formed in `dtype`)"""
+    return gram_measure(gram(G, dtype), dtype)
+
+
+def jacobi_pair(G, tol, dtype=LD, wp=None):
+    """(measure, G J, J) of one block pair, steps 1-4 of jsvd_pair_kernel on the pair's k <= 64 columns (the first wp of them are the first
+    block's and sit in slots 0 .., the others in slots 32 ..; default: min(k, 32)): the Gram matrix S; the measure over the live pairs,
+    at or below tol nothing happens (J = I); else cyclic sweeps (at most 16) of 63 round-robin steps of 32 disjoint rotations each on S,
+    the angles of a step taken from S as the step found it, the root of smaller modulus of tan^2 + 2 zeta tan - 1 = 0, a pair rotated
+    only when live and above tol; J <- J R with cos written as 1 - s^2 / (1 + c); a sweep that leaves the measure at or below tol is
+    the last."""
+    G = arr(G, dtype)
+    k = G.shape[1]
+    wp = min(k, JS_SLOTS // 2) if wp is None else wp
+    col = {**{i: i for i in range(wp)}, **{JS_SLOTS // 2 + i: wp + i for i in range(k - wp)}}         # slot -> column
+    S = gram(G, dtype)
+    J = arr(np.eye(k), dtype)
+    off = gram_measure(S, dtype)
+    if not off > tol:
+        return off, G, J
+    one = S[0, 0] * 0 + 1
+    for _ in range(JS_INNER_MAX):
+        for st in range(JS_SLOTS - 1):
+            rots = []
+            for q in range(JS_SLOTS // 2):
+                si, sj = js_inner_pair(st, q)
+                if si not in col or sj not in col:
+                    continue
+                i, j = col[si], col[sj]
+                a, b, g = S[i, i], S[j, j], S[i, j]
+                if js_live(a, b) and abs(g) > tol * (_root(a, dtype) * _root(b, dtype)):
+                    zeta = (b - a) / (2 * g)
+                    tn = (one if zeta >= 0 else -one) / (abs(zeta) + _root(1 + zeta * zeta, dtype))
+                    c = 1 / _root(1 + tn * tn, dtype)
+                    s = c * tn
+                    rots.append((i, j, c, s, s * s / (1 + c)))
+            for i, j, c, s, h in rots:
+                ci, cj = S[:, i].copy(), S[:, j].copy()
+                S[:, i], S[:, j] = c * ci - s * cj, s * ci + c * cj
+                ri, rj = S[i].copy(), S[j].copy()
+                S[i], S[j] = c * ri - s * rj, s * ri + c * rj
+                S[i, j] = S[j, i] = S[i, j] * 0
+                ji, jj = J[:, i].copy(), J[:, j].copy()
+                J[:, i], J[:, j] = ji - (h * ji + s * jj), jj + (s * ji - h * jj)
+        if not gram_measure(S, dtype) > tol:
+            break
+    GJ = G * 0
+    for l in range(k):
+        GJ += G[:, l][:, None] * J[l][None, :]
+    return off, GJ, J

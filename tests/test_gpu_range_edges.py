@@ -34,7 +34,7 @@ import test_gpu_batched as tb
 import test_gpu_batched_pivot as tbp
 import test_gpu_panel_cqr as tcq
 import test_gpu_panel_fused as tpf
-from gpu_util import dev, host, zeros
+from gpu_util import dev, host, within, zeros
 from test_gpu_downdate import _tphqrt
 from test_gpu_kernels import _cholqr_leaf
 from test_gpu_lstsq import _cond_matrix
@@ -59,10 +59,7 @@ def U(seed, *shape):
 
 def _within(tag, got, ref, cap=INF):
     """got <= min(max(FACTOR * ref, eps), cap); prints the ratio"""
-    factor = 2.0 * MEASURED[tag] if tag in MEASURED else 4.0
-    bound = min(max(factor * ref, EPS), cap)
-    print(f"RATIO {tag}{_SCALE[0]}: {got:.3e} is {got / max(ref, EPS / 4):.2f} x the float64 reference {ref:.3e}; bound {bound:.3e}")
-    assert np.isfinite(got) and got <= bound, (tag, got, ref, bound)
+    within(tag, got, ref, cap, MEASURED, _SCALE[0])
 
 
 def _factor_measures(A, F, tau, jpvt=None):
